@@ -277,6 +277,30 @@ def also_measurements(pkg, torch):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6    # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0x0D0D5EED       # the fixed pixel sample when the whole output does not fit
+
+
+def dump_outputs(out_dir, color, seeds=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as .npy files in `out_dir`.
+    color: the three colour planes (float32); seeds: the four SFC32 seed planes (uint32, written as float64, which is exact).
+    The whole planes when they fit DUMP_BUDGET_BYTES, otherwise the same seeded sample of pixels (ascending pixel index) from
+    every plane, so that two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    color = np.stack([np.asarray(p, np.float32) for p in color])
+    arrays = {"color": color}
+    if seeds is not None:
+        arrays["seeds"] = np.stack([np.asarray(p, np.uint32) for p in seeds]).astype(np.float64)
+    n_pixels = color[0].size
+    per_pixel = sum(a.itemsize * a.shape[0] for a in arrays.values())
+    if n_pixels * per_pixel > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pixels, DUMP_BUDGET_BYTES // per_pixel, replace=False))
+        arrays = {name: a.reshape(a.shape[0], -1)[:, keep] for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def pick_stripe(height, world):
     """Stripe height that deals every rank the same number of rows, closest to the 8-row tile of the kernel."""
     for s in (8, 10, 6, 12, 5, 4, 15, 16, 3, 2, 1):
@@ -323,6 +347,10 @@ def main():
                     help="samples per launch of the untimed clock ramp before the warm-up (capped at the workload's spp); 0 = the workload's "
                          "own spp, so that EVERY launch of the process is a launch of the workload -- what tools/pmc_kernels.sh passes: a "
                          "per-kernel mean of a profile must not mix two launch sizes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left for the caller to DIR/<name>.npy: color.npy (float32, "
+                         "[3][rows][width]) and, on one GPU, seeds.npy (the four SFC32 seed planes as float64); N > 1: rank 0's gathered "
+                         "image only.  At most 64 MB in all: past that, the same seeded sample of pixels from every plane ([planes][pixels])")
     args = ap.parse_args()
 
     import torch
@@ -500,6 +528,12 @@ def main():
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / max(args.steps, 1)
     stats = ctx.stats()
+    if args.dump_outputs:
+        if world == 1:
+            result = ctx.download_state()
+            dump_outputs(args.dump_outputs, result[:3], result[3:])
+        elif rank == 0:
+            dump_outputs(args.dump_outputs, gather.full.cpu().numpy())
 
     per_rank, render_only_ms, k_only = None, None, 0
     if world > 1:

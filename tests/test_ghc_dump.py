@@ -1,7 +1,8 @@
 """tools/compare_ghc_dump.py, the MI355X side of the parity experiment, fed dumps in the format haskell/dump/Dump.hs writes -- made here
 FROM THE ORACLE (a real one needs a GHC build of the reference, which does not exist in this container): a faithful dump must pass every
 assumption; one with a deliberately broken generator must be named by its assumption.  Also: the numpy SFC32 the comparator diagnoses
-with equals the oracle's, the file format round-trips, and the Haskell program's cabal patch applies to the reference tree."""
+with equals the oracle's, the file format round-trips, and the Haskell program's cabal patch applies to the reference tree (its
+line-fingerprint stand-in, tests/reftree.py)."""
 import importlib.util
 import os
 import shutil
@@ -9,6 +10,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+import reftree
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DUMP_DIR = os.path.join(ROOT, "haskell-path-tracer_amd", "haskell", "dump")
@@ -90,15 +93,15 @@ def test_command_line_and_exit_codes(tmp_path):
     assert ko.returncode == 1 and "first failure: A1" in ko.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference") or shutil.which("patch") is None, reason="needs the reference tree and patch(1)")
+@pytest.mark.skipif(shutil.which("patch") is None, reason="needs patch(1)")
 def test_the_dump_programs_cabal_patch_applies_and_its_source_names_what_the_reader_expects(tmp_path):
-    shutil.copy("/root/reference/tracer.cabal", tmp_path / "tracer.cabal")
+    reftree.write_tree(tmp_path, ["tracer.cabal"])
     res = subprocess.run(["patch", "-p1", "-i", os.path.join(DUMP_DIR, "tracer.cabal.diff")], cwd=tmp_path, capture_output=True, text=True)
     assert res.returncode == 0 and "fuzz" not in res.stdout, res.stdout + res.stderr
     cabal = open(tmp_path / "tracer.cabal").read()
     assert "executable ptmi-dump" in cabal and "accelerate-llvm-native" in cabal.split("executable ptmi-dump")[1]
     # ... also on top of the wiring patch of haskell/patches
-    shutil.copy("/root/reference/tracer.cabal", tmp_path / "tracer.cabal")
+    reftree.write_tree(tmp_path, ["tracer.cabal"])
     for diff in (os.path.join(ROOT, "haskell-path-tracer_amd", "haskell", "patches", "tracer.cabal.diff"), os.path.join(DUMP_DIR, "tracer.cabal.diff")):
         assert subprocess.run(["patch", "-p1", "-i", diff], cwd=tmp_path, capture_output=True, text=True).returncode == 0
     src = open(os.path.join(DUMP_DIR, "Dump.hs")).read()

@@ -1,4 +1,4 @@
-"""haskell/patches/*.diff apply to the reference tree (CPU; skipped where /root/reference does not exist, e.g. on the GPU box).
+"""haskell/patches/*.diff apply to the reference tree (CPU), represented by the line-fingerprint stand-ins of tests/reftree.py.
 The patched tree is never compiled -- no GHC anywhere -- this only keeps the patches from rotting against the files they edit."""
 import os
 import shutil
@@ -6,18 +6,17 @@ import subprocess
 
 import pytest
 
+import reftree
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
 PATCHES = os.path.join(ROOT, "haskell-path-tracer_amd", "haskell", "patches")
 FILES = {"Main.hs.diff": "app/Main.hs", "World.hs.diff": "src/Scene/World.hs", "tracer.cabal.diff": "tracer.cabal"}
-NEEDS_REFERENCE = pytest.mark.skipif(not os.path.isdir(REFERENCE) or shutil.which("patch") is None, reason="needs the reference tree and patch(1)")
+NEEDS_PATCH = pytest.mark.skipif(shutil.which("patch") is None, reason="needs patch(1)")
 
 
-@NEEDS_REFERENCE
+@NEEDS_PATCH
 def test_patches_apply_to_the_reference_tree(tmp_path):
-    for rel in FILES.values():
-        os.makedirs(os.path.dirname(os.path.join(tmp_path, rel)), exist_ok=True)
-        shutil.copy(os.path.join(REFERENCE, rel), os.path.join(tmp_path, rel))
+    reftree.write_tree(tmp_path, FILES.values())
     for name, rel in FILES.items():
         dry = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(PATCHES, name)], cwd=tmp_path, capture_output=True, text=True)
         assert dry.returncode == 0, name + ": " + dry.stdout + dry.stderr
@@ -32,20 +31,19 @@ def test_patches_apply_to_the_reference_tree(tmp_path):
     assert "extra-libraries: ptmi" in cabal and "flag Hip" in cabal and "-DUSE_HIP_BACKEND" in cabal
 
 
-@NEEDS_REFERENCE
+@NEEDS_PATCH
 def test_the_resident_wiring_applies_to_a_pristine_main(tmp_path):
     """patches/Main.resident.diff -- the alternative to Main.hs.diff: Result carries the iteration count, the batch is
     one HIP.renderResident, the colour planes come down under the lock.  Applies to the reference's app/Main.hs without fuzz; every
     Accelerate line it touches is kept under #else."""
-    os.makedirs(tmp_path / "app")
-    shutil.copy(os.path.join(REFERENCE, "app/Main.hs"), tmp_path / "app" / "Main.hs")
+    reftree.write_tree(tmp_path, ["app/Main.hs"])
     patch = os.path.join(PATCHES, "Main.resident.diff")
     dry = subprocess.run(["patch", "-p1", "--dry-run", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
     assert dry.returncode == 0, dry.stdout + dry.stderr
     real = subprocess.run(["patch", "-p1", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
     assert real.returncode == 0 and "fuzz" not in real.stdout and "offset" not in real.stdout, real.stdout
     main = open(tmp_path / "app" / "Main.hs").read()
-    original = open(os.path.join(REFERENCE, "app/Main.hs")).read()
+    original = reftree.stand_in("app/Main.hs")
     assert main.count("#if defined(USE_HIP_BACKEND)") == main.count("#endif") == 9           # (the reference's own backend #ifdef is now an #elif of the first)
     for call in ("HIP.renderResident hip", "HIP.resetOutput hip", "HIP.reseedResident hip", "HIP.downloadColor hip", "HIP.synchronize hip", "HIP.initialise 0 screenWidth screenHeight"):
         assert call in main, call
