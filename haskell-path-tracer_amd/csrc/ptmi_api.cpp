@@ -25,6 +25,13 @@ using namespace ptmi;
 // render Inline with contracted arithmetic: the second object made from ptmi_inline.hip (see its last lines)
 extern "C" int ptmi_contracted_launch_inline(const void *args, int variant, void *stream);
 
+// A device block of the context: null <=> 0 bytes.  grow() and release() below keep that, and that nothing the stream may still read is freed.
+struct DeviceBlock {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
 struct ptmi_ctx {
     std::mutex mu;
     int device = 0;
@@ -38,16 +45,16 @@ struct ptmi_ctx {
     int rows_local = 0;
 
     Planes owned{};          // seven planes carved from owned_block
-    void *owned_block = nullptr;
+    DeviceBlock owned_block;
     Planes bound{};
     bool use_bound = false;
 
-    float4 *d_scene = nullptr;
+    DeviceBlock d_scene;     // float4s: pack_scene
     int n_spheres = 0, n_planes = 0;
 
-    unsigned long long *d_live = nullptr;
-    unsigned int *d_work = nullptr;
-    unsigned int *d_iters = nullptr;
+    DeviceBlock d_live;      // unsigned long long
+    DeviceBlock d_work;      // unsigned int
+    DeviceBlock d_iters;     // unsigned int
     uint64_t nominal = 0, samples = 0;
 
     bool timing = false;
@@ -56,7 +63,7 @@ struct ptmi_ctx {
     // stream of its own, beside the persistent launch.  d_tail_start: where that end begins (written by the order kernel).
     hipStream_t tail_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned int *d_tail_start = nullptr;
+    DeviceBlock d_tail_start;   // unsigned int
     int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
     bool ev_valid = false;
     int variant = 0;
@@ -64,26 +71,24 @@ struct ptmi_ctx {
 
     // cost-ordered dispatch of the tiled kernels: what every quad of tiles cost in the last launch with this key, and
     // the order (most expensive first) later launches with the same key use.  order_state = launches made with this key
-    unsigned int *d_quad_cost = nullptr, *d_quad_order = nullptr, *d_quad_class = nullptr;
-    unsigned int quad_capacity = 0;
+    DeviceBlock d_quad_cost, d_quad_order, d_quad_class;   // unsigned int per quad
     int order_state = 0;
-    unsigned int *d_chunk_done = nullptr;      // sample chunks of the tiled Inline kernel: one word per tile workgroup
-    unsigned int chunk_capacity = 0;
+    DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup
+    unsigned int chunk_capacity = 0;           // ... that many (the ticket counter's line follows)
     struct OrderKey { ptmi_camera cam; uint64_t scene_version; int dims[8]; } order_key{};
     uint64_t scene_version = 0;
 
     // scratch for ptmi_render1 / point queries
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DeviceBlock scratch;
 
     // wavefront Streams (scenes with the GLASS extension): two ray streams + {next length, dropped}
     bool has_glass = false;
-    void *queue_block = nullptr;
-    size_t queue_capacity = 0;
-    void *hit_block = nullptr;       // stream form: the start hits of the pixels, in regions (HitList)
-    size_t hit_capacity = 0;
-    unsigned int *d_hit_counts = nullptr;   // ... records per region
-    unsigned long long *d_hit_missed = nullptr;   // ... and the pixels of every region that have none
+    DeviceBlock queue_block;
+    size_t queue_capacity = 0;       // ... rays per stream
+    DeviceBlock hit_block;           // stream form: the start hits of the pixels, in regions (HitList)
+    size_t hit_capacity = 0;         // ... slots
+    DeviceBlock d_hit_counts;        // ... records per region (unsigned int)
+    DeviceBlock d_hit_missed;        // ... and the pixels of every region that have none (unsigned long long)
     unsigned int hit_regions = 0;
     // The start-hit list is a function of (camera, scene, shape, partition, dispatch order) only -- every sample of a pixel
     // shoots the same primary ray, in every call -- so it is kept until one of them changes.
@@ -91,35 +96,30 @@ struct ptmi_ctx {
     bool hit_list_valid = false;
     uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
     uint64_t hit_split_pixels = 0;          // pixels whose glass primary hit the list replaced by its children's hits
-    void *d_snapshots = nullptr;     // stream form, split kernel: the seed every item starts from
-    size_t snapshot_bytes = 0;
+    DeviceBlock d_snapshots;         // stream form, split kernel: the seed every item starts from
     int cus = 0;                     // compute units of the device (persistent grids)
     size_t device_memory = (size_t)64 << 30;   // bytes of the device (budget of the stream form's seed snapshots)
-    void *tree_stack = nullptr;      // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
-    size_t tree_stack_bytes = 0;
-    unsigned int *d_region_done = nullptr;   // stream form, ordered passes: items published per region
-    unsigned int region_done_words = 0;
+    DeviceBlock tree_stack;          // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
+    DeviceBlock d_region_done;       // stream form, ordered passes: items published per region (unsigned int)
     int opt_ordered_passes = 0;      // PTMI_OPT_ORDERED_PASSES: 0 = automatic, 1 = off, k = k passes
     int opt_pass_handoff = 0;        // PTMI_OPT_PASS_HANDOFF: 0 = release / acquire once per (region, pass); 1 = the fence-free write-through hand-off
-    int *d_pass_first = nullptr;     // stream form, split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
+    DeviceBlock d_pass_first;        // stream form, split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
     std::vector<int> pass_first_host;   // ... what the device block holds
-    unsigned int *d_qcount = nullptr;
+    DeviceBlock d_qcount;            // stream form: kLvWords counter words (unsigned int)
     uint64_t rays_dropped = 0;
     uint64_t rays_truncated = 0;
     uint64_t rays_spilled = 0;       // stream form: children that found the wave's ring full and went through HBM
     uint64_t rays_overflowed = 0;    // ... and its spill queue too: traced by an overflow level
-    void *spill_block = nullptr;     // stream form: the waves' spill queues
-    size_t spill_capacity = 0;
+    DeviceBlock spill_block;         // stream form: the waves' spill queues
     uint64_t live_host = 0;        // live rays counted on the host (wavefront path)
-    unsigned long long *d_stream_counters = nullptr;   // kScWords device counters of the per-pixel Streams kernels
+    DeviceBlock d_stream_counters;   // kScWords device counters of the per-pixel Streams kernels
 
     // options of render Streams (ptmi_set_option)
     int opt_seed_rule = PTMI_SEED_AUTO;              // resolved per scene: effective_seed_rule()
     int opt_step_cap = kStreamStepCapDefault;
     int opt_capacity = 4;
     int grown_capacity = 0;                          // stream form with GLASS: rays per pixel the overflow streams have been GROWN to after a call would have dropped children (0: never)
-    void *colour_backup = nullptr;                   // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
-    size_t colour_backup_bytes = 0;
+    DeviceBlock colour_backup;                       // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
     int opt_form = PTMI_FORM_AUTO;
     int opt_batch = 0;
     int opt_spp_chunks = 0;                    // 0 = automatic
@@ -143,6 +143,15 @@ struct ptmi_ctx {
     uint64_t chain_counter = 0;
     int opt_chain_slots = 0;                   // PTMI_OPT_CHAIN_SLOTS: 0 = automatic
     ptmi_chain_stats chain_stats{};
+
+    // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
+    template <class F> void each_block(F &&f)
+    {
+        for (DeviceBlock *b : {&owned_block, &d_scene, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
+                               &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
+            f(*b);
+    }
 };
 
 namespace {
@@ -225,12 +234,35 @@ bool too_many_pixels(int width, int height) { return (unsigned long long)width *
 
 Planes &active(ptmi_ctx *c) { return c->use_bound ? c->bound : c->owned; }
 
-int ensure_scratch(ptmi_ctx *c, size_t bytes)
+// The one allocation of a DeviceBlock (which must be empty).  On failure it stays empty and the runtime's sticky slot is cleared.
+hipError_t allocate(DeviceBlock &b, size_t bytes)
 {
-    if (bytes <= c->scratch_bytes) return PTMI_OK;
-    if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-    PTMI_HIP(c, hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.bytes = bytes;
+    else { (void)hipGetLastError(); b.p = nullptr; }
+    return e;
+}
+
+void release(DeviceBlock &b)
+{
+    if (b.p) (void)hipFree(b.p);
+    b = DeviceBlock{};
+}
+
+// `b` holds at least `bytes` (its contents are not kept).  A block that is replaced goes only once the stream is drained; with none
+// held nothing on the stream can read it (the tail stream has joined c->stream before any call returns).  If the allocation fails the
+// block is empty.
+int grow(ptmi_ctx *c, DeviceBlock &b, size_t bytes, const char *what)
+{
+    if (bytes <= b.bytes) return PTMI_OK;
+    if (b.p) {
+        PTMI_HIP(c, hipStreamSynchronize(c->stream));
+        release(b);
+    }
+    const hipError_t e = allocate(b, bytes);
+    if (e != hipSuccess)
+        return fail(c, e == hipErrorOutOfMemory ? PTMI_ENOMEM : PTMI_EHIP,
+                    std::string(what) + ": hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
     return PTMI_OK;
 }
 
@@ -432,138 +464,159 @@ int pass_group_table(int option, const int *first, int passes, int table[kMaxStr
 //   * GLASS (or PTMI_OPT_STREAM_BATCH > 0): streams_split_kernel -- items of (start hit, sample range), children through the
 //     waves' LDS rings.  The predicate `null state` (Trace.hs:166-170) is the overflow stream's length: read back ONCE, after
 //     the launch; only if children really travelled through HBM does the host play `awhile`, one launch per overflow level.
-int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_camera &camera)
-{
-    const size_t n = (size_t)a.rows_local * a.width;
-    if (n == 0 || n_spp <= 0) return PTMI_OK;
-    if (n > 0x3ffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");   // 32-bit byte offsets into the planes
-    const bool ordered = !c->has_glass && (c->opt_batch == 0 || a.seed_from_result);
-    const unsigned int n_regions = streams_regions(a.width, a.rows_local);
-    const unsigned int region_slots = ordered ? 64u : 128u;    // a glass primary hit contributes up to two start hits
-    const size_t hit_slots = (size_t)n_regions * region_slots;
-    if (hit_slots > 0xfffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");
-    if (hit_slots > c->hit_capacity || n_regions > c->hit_regions) {
-        PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->hit_block) { (void)hipFree(c->hit_block); c->hit_block = nullptr; c->hit_capacity = 0; }
-        if (c->d_hit_counts) { (void)hipFree(c->d_hit_counts); c->d_hit_counts = nullptr; c->hit_regions = 0; }
-        if (c->d_hit_missed) { (void)hipFree(c->d_hit_missed); c->d_hit_missed = nullptr; }
-        c->hit_list_valid = false;
-        PTMI_HIP(c, hipMalloc(&c->hit_block, (size_t)(kHitListWords + 1) * hit_slots * 4));      // the records, and behind them one key word per slot
-        c->hit_capacity = hit_slots;
-        PTMI_HIP(c, hipMalloc(&c->d_hit_counts, (size_t)n_regions * sizeof(unsigned int)));
-        PTMI_HIP(c, hipMalloc(&c->d_hit_missed, (size_t)n_regions * sizeof(unsigned long long)));
-        c->hit_regions = n_regions;
+// One call: its steps, and what they share.
+struct StreamCall {
+    ptmi_ctx *c;
+    RenderArgs &a;
+    int n_spp;
+    size_t n;                         // pixels of the part
+    unsigned int n_regions, region_slots;
+    size_t hit_slots;
+    int cus;
+    bool fresh_list = false;          // the start-hit list was built by this call
+    HitList hits{};
+    ItemArgs it{};
+    // the split kernel
+    unsigned int grid = 0, first_block = 0, level_grid_max = 0;
+    size_t floor_slots = 0;           // the overflow streams hold at least every wave's static block
+    int cap_rays = 0;                 // rays per pixel the overflow streams are sized for ...
+    size_t capacity = 0;              // ... and the rays each of the two holds
+    RayQueue q[2]{};
+    std::vector<unsigned int> base{}, raw{};   // per level (mod kLvMaxLevels): where its reserved blocks start; the counters read back
+    size_t plane_bytes = 0, cost_bytes = 0;
+    bool can_redo = false;
+
+    int start_hit_list(const ptmi_camera &camera);
+    int ordered_passes();
+    int split_setup();
+    int copy_colour(bool restore);
+    int read_counters(int levels);
+    int overflow_levels(unsigned long long &overflowed);
+    int redo_longer(bool *again);
+    int fold_counters(unsigned long long overflowed);
+
+    unsigned int *qcount() const { return c->d_qcount.as<unsigned int>(); }
+    static size_t cursor_of(int level) { return (size_t)(kLvCursor + kLvPerLevel * (level % kLvMaxLevels)) * kCounterStride; }
+    unsigned long long emitted_of(int level) const {         // children the level stored: the sum of its shards (read back into `raw`)
+        unsigned long long total = 0;
+        for (int k = 0; k < kLvEmitShards; ++k) total += raw[cursor_of(level) + (size_t)(2 + k) * kCounterStride];
+        return total;
     }
-    if (!c->d_qcount) PTMI_HIP(c, hipMalloc(&c->d_qcount, (size_t)kLvWords * sizeof(unsigned int)));
-    HitList hits;
-    hits.base = static_cast<uint32_t *>(c->hit_block);
+    size_t slots_for(int rays_per_pixel) const { return n * (size_t)rays_per_pixel < floor_slots ? floor_slots : n * (size_t)rays_per_pixel; }
+};
+
+// The start-hit list: sized, keyed, and launched unless the list of an earlier call stands.  It is a function of (camera, scene, shape,
+// partition, dispatch order) only -- every sample of a pixel shoots the same primary ray, in every call.
+int StreamCall::start_hit_list(const ptmi_camera &camera)
+{
+    if (hit_slots > c->hit_capacity || n_regions > c->hit_regions) {
+        c->hit_list_valid = false;
+        c->hit_capacity = 0; c->hit_regions = 0;
+        // the records, and behind them one key word per slot
+        if (int rc = grow(c, c->hit_block, (size_t)(kHitListWords + 1) * hit_slots * 4, "the start-hit list")) return rc;
+        if (int rc = grow(c, c->d_hit_counts, (size_t)n_regions * sizeof(unsigned int), "the start-hit list's counts")) return rc;
+        if (int rc = grow(c, c->d_hit_missed, (size_t)n_regions * sizeof(unsigned long long), "the start-hit list's misses")) return rc;
+        c->hit_capacity = hit_slots; c->hit_regions = n_regions;
+    }
+    if (int rc = grow(c, c->d_qcount, (size_t)kLvWords * sizeof(unsigned int), "the stream form's counters")) return rc;
+    hits.base = c->hit_block.as<uint32_t>();
     hits.slot_key = hits.base + (size_t)kHitListWords * c->hit_capacity;
-    hits.counts = c->d_hit_counts;
-    hits.missed = c->d_hit_missed;
+    hits.counts = c->d_hit_counts.as<unsigned int>();
+    hits.missed = c->d_hit_missed.as<unsigned long long>();
     hits.region_slots = region_slots;
     hits.n_regions = n_regions;
     // the statistics accumulate on the device over the whole call; cursors start from zero
-    PTMI_HIP(c, hipMemsetAsync(c->d_qcount, 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
-    auto cursor_of = [&](int level) { return (size_t)(kLvCursor + kLvPerLevel * (level % kLvMaxLevels)) * kCounterStride; };
+    PTMI_HIP(c, hipMemsetAsync(qcount(), 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
     ptmi_ctx::HitKey key{};
     key.cam = camera; key.scene_version = c->scene_version; key.order_generation = a.quad_order ? c->order_generation : 0;
     const int key_dims[8] = {a.width, a.height, a.rows_local, a.stripe_rows, a.n_parts, a.part, a.quad_order ? 1 : 0, 0};
     std::memcpy(key.dims, key_dims, sizeof key_dims);
     key.region_slots = region_slots; key.cap_allows_split = a.stream_step_cap >= 3 ? 1 : 0; key.planes_r = nullptr;
-    const bool list_kept = c->hit_list_valid && std::memcmp(&key, &c->hit_key, sizeof key) == 0;
-    // A list built by THIS call counts as kept by later ones only if this call gets to its end: what the host keeps beside it (the split pixels'
-    // count, read back below) is only then the list's.  Any error return on the way leaves the list invalid.
-    struct ListGuard { ptmi_ctx *c; bool fresh; bool done = false; ~ListGuard() { if (fresh && !done) c->hit_list_valid = false; } } guard{c, !list_kept};
-    if (!list_kept) {
+    fresh_list = !(c->hit_list_valid && std::memcmp(&key, &c->hit_key, sizeof key) == 0);
+    if (fresh_list) {
         c->hit_list_valid = false;
-        PTMI_HIP(c, launch_streams_primary(a, hits, c->d_qcount, c->stream));
+        PTMI_HIP(c, launch_streams_primary(a, hits, qcount(), c->stream));
         c->hit_key = key; c->hit_list_valid = true;
     }
-    ItemArgs it{};
-    it.hits = hits;
-    it.n_positions = n_regions / 4u;
-    it.passes = 1; it.group_first = nullptr; it.groups = 0;
-    it.n_slots = (unsigned int)hit_slots;
-    it.stats = c->d_qcount;
-    auto tickets_of = [&](int launch) { return c->d_qcount + (size_t)(kLvTickets + 8 * launch) * kCounterStride; };
-    const int cus = c->cus > 0 ? c->cus : 256;
-    if (ordered) {
-        // One lane renders a pixel's samples in order, so an item is a serial chain and the end of a launch is as long as its last
-        // items: with three items per lane (1080p) a quarter of the wave-time of the launch lay after the first wave had ended.
-        // The samples are therefore cut into ordered passes INSIDE the one launch (streams_pixels_kernel): a pixel's next pass is
-        // handed out once its previous one has been published.
-        const unsigned int grid_full = (unsigned int)(cus * 4 * streams_pixels_waves());
-        const unsigned long long lanes = 64ull * grid_full;
-        int passes = 1;
-        if (c->opt_ordered_passes > 0) passes = c->opt_ordered_passes;    // (1 = off: one pass, no hand-off between waves inside the launch)
-        else if (c->opt_batch > 0) passes = (n_spp + c->opt_batch - 1) / c->opt_batch;     // PTMI_OPT_STREAM_BATCH: samples per item
-        else if (c->opt_pass_handoff == 0 && n < 3ull * lanes && n_spp >= 256) passes = n_spp / 64 < 8 ? n_spp / 64 : 8;
-        // (automatic only with the FENCED hand-off -- release / acquire at agent scope once per region and pass, what the memory model
-        // promises; the fence-free hand-off of rounds 3-5, PTMI_OPT_PASS_HANDOFF = 1, is measured valid, not promised, and never chosen
-        // without the caller's explicit PTMI_OPT_ORDERED_PASSES)
-        // (few, LONG items per lane: items of >= 64 samples, at most 8 passes.  The kernel of the ordered passes is 3 % slower per trip
-        // than the one-pass kernel, and an item costs its refill and its seven stores.  1080p, S16, ms with 1 / 2 / 4 / 8 / 16 / 32 passes:
-        // 64 spp 4.46 / 4.62 / 4.63 / 4.84 / 4.83 / 4.86; 256 spp 17.49 / 17.24 / 16.99 / 17.11 / 17.70 / 18.96; 1024 spp 69.7 / 68.1 / 66.0 /
-        // 64.9 / 65.3 / 66.8.  With the per-pixel tail below, which only a one-pass launch has, the whole 1080p image -- 4.5 pixels per lane --
-        // is better off in one pass: 256 spp 16.60 against 17.19 ms with four passes, 512 spp 32.86 against 33.48, 1024 spp equal; one of 8
-        // parts of a 4K image -- 2.3 pixels per lane -- is not: 1024 spp 38.98 against 36.10 with eight passes.  Hence 3 pixels per lane.)
-        if (passes > 64) passes = 64;
-        const int most = n_spp / streams_min_pass_samples();   // a pass holds at least that many samples
-        if (passes > most) passes = most;
-        if (passes < 1) passes = 1;
-        it.passes = passes;                                // (ordered passes wait for each other: every pass on its own, no group table)
-        it.fenced = c->opt_pass_handoff == 0 ? 1 : 0;
-        if (passes > 1 && n_regions >= (1u << 26)) return fail(c, PTMI_ELIMIT, "image too large for ordered passes (2^26 regions)");
-        it.chunk_cursor = tickets_of(0);
-        // THE TAIL.  A lane renders a pixel's whole sample chain, so the persistent launch ends as its last items do: its waves end between
-        // 70 and 100 % of it.  The cheapest quads of the dispatch order -- the order kernel marks where they begin, on the device -- are
-        // therefore left to the per-pixel chain kernel, launched beside the persistent kernel on a low-priority stream: its waves (one
-        // tile each) take the slots the persistent waves leave as they end.  Every pixel is rendered by exactly one of the two kernels,
-        // by the same arithmetic: no result depends on where the boundary lies.
-        // (Only while a pixel's samples are ONE item: where they are cut into ordered passes the end of the launch is short already, and a
-        // tail wave would render its tile's many samples in one piece -- 1080p / 256 spp: 16.99 ms with four passes, 17.86 with a tail beside them.)
-        const unsigned int *tail = (passes == 1 && c->opt_tail_permille != 0 && a.quad_order && c->d_tail_start && quad_positions(a.width, a.rows_local) > 0) ? c->d_tail_start : nullptr;
-        if (tail && !c->tail_stream) {
-            int least = 0, greatest = 0;
-            PTMI_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            PTMI_HIP(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, least));
-            PTMI_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            PTMI_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
-        it.tail_start = tail;
-        PTMI_HIP(c, launch_streams_advance_missed(a, hits, n_spp, tail, c->stream));
-        PTMI_HIP(c, hipMemsetAsync(c->d_iters, 0, kItersBytes, c->stream));
-        if (tail) {
-            PTMI_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-            PTMI_HIP(c, hipStreamWaitEvent(c->tail_stream, c->ev_fork, 0));
-        }
+    return PTMI_OK;
+}
 
-        if (passes > 1) {
-            if (n_regions > c->region_done_words) {
-                PTMI_HIP(c, hipStreamSynchronize(c->stream));
-                if (c->d_region_done) { (void)hipFree(c->d_region_done); c->d_region_done = nullptr; c->region_done_words = 0; }
-                PTMI_HIP(c, hipMalloc(&c->d_region_done, (size_t)n_regions * sizeof(unsigned int)));
-                c->region_done_words = n_regions;
-            }
-            PTMI_HIP(c, hipMemsetAsync(c->d_region_done, 0, (size_t)n_regions * sizeof(unsigned int), c->stream));
-            it.region_done = c->d_region_done;
-        }
-        unsigned int grid = grid_full;
-        const unsigned long long tickets = (unsigned long long)n_regions * (unsigned long long)passes;
-        if (grid > tickets) grid = (unsigned int)(tickets < 1 ? 1 : tickets);
-        PTMI_HIP(c, launch_streams_pixels(a, it, grid, c->stream));
-        if (tail) {
-            PTMI_HIP(c, launch_render_streams_tail(a, tail, c->tail_stream));
-            PTMI_HIP(c, hipEventRecord(c->ev_join, c->tail_stream));
-            PTMI_HIP(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        }
-        guard.done = true;
-        return PTMI_OK;
+// One lane renders a pixel's samples in order, so an item is a serial chain and the end of a launch is as long as its last
+// items: with three items per lane (1080p) a quarter of the wave-time of the launch lay after the first wave had ended.
+// The samples are therefore cut into ordered passes INSIDE the one launch (streams_pixels_kernel): a pixel's next pass is
+// handed out once its previous one has been published.
+int StreamCall::ordered_passes()
+{
+    const unsigned int grid_full = (unsigned int)(cus * 4 * streams_pixels_waves());
+    const unsigned long long lanes = 64ull * grid_full;
+    int passes = 1;
+    if (c->opt_ordered_passes > 0) passes = c->opt_ordered_passes;    // (1 = off: one pass, no hand-off between waves inside the launch)
+    else if (c->opt_batch > 0) passes = (n_spp + c->opt_batch - 1) / c->opt_batch;     // PTMI_OPT_STREAM_BATCH: samples per item
+    else if (c->opt_pass_handoff == 0 && n < 3ull * lanes && n_spp >= 256) passes = n_spp / 64 < 8 ? n_spp / 64 : 8;
+    // (automatic only with the FENCED hand-off -- release / acquire at agent scope once per region and pass, what the memory model
+    // promises; the fence-free hand-off of rounds 3-5, PTMI_OPT_PASS_HANDOFF = 1, is measured valid, not promised, and never chosen
+    // without the caller's explicit PTMI_OPT_ORDERED_PASSES)
+    // (few, LONG items per lane: items of >= 64 samples, at most 8 passes.  The kernel of the ordered passes is 3 % slower per trip
+    // than the one-pass kernel, and an item costs its refill and its seven stores.  1080p, S16, ms with 1 / 2 / 4 / 8 / 16 / 32 passes:
+    // 64 spp 4.46 / 4.62 / 4.63 / 4.84 / 4.83 / 4.86; 256 spp 17.49 / 17.24 / 16.99 / 17.11 / 17.70 / 18.96; 1024 spp 69.7 / 68.1 / 66.0 /
+    // 64.9 / 65.3 / 66.8.  With the per-pixel tail below, which only a one-pass launch has, the whole 1080p image -- 4.5 pixels per lane --
+    // is better off in one pass: 256 spp 16.60 against 17.19 ms with four passes, 512 spp 32.86 against 33.48, 1024 spp equal; one of 8
+    // parts of a 4K image -- 2.3 pixels per lane -- is not: 1024 spp 38.98 against 36.10 with eight passes.  Hence 3 pixels per lane.)
+    if (passes > 64) passes = 64;
+    const int most = n_spp / streams_min_pass_samples();   // a pass holds at least that many samples
+    if (passes > most) passes = most;
+    if (passes < 1) passes = 1;
+    it.passes = passes;                                // (ordered passes wait for each other: every pass on its own, no group table)
+    it.fenced = c->opt_pass_handoff == 0 ? 1 : 0;
+    if (passes > 1 && n_regions >= (1u << 26)) return fail(c, PTMI_ELIMIT, "image too large for ordered passes (2^26 regions)");
+    // THE TAIL.  A lane renders a pixel's whole sample chain, so the persistent launch ends as its last items do: its waves end between
+    // 70 and 100 % of it.  The cheapest quads of the dispatch order -- the order kernel marks where they begin, on the device -- are
+    // therefore left to the per-pixel chain kernel, launched beside the persistent kernel on a low-priority stream: its waves (one
+    // tile each) take the slots the persistent waves leave as they end.  Every pixel is rendered by exactly one of the two kernels,
+    // by the same arithmetic: no result depends on where the boundary lies.
+    // (Only while a pixel's samples are ONE item: where they are cut into ordered passes the end of the launch is short already, and a
+    // tail wave would render its tile's many samples in one piece -- 1080p / 256 spp: 16.99 ms with four passes, 17.86 with a tail beside them.)
+    const unsigned int *tail = (passes == 1 && c->opt_tail_permille != 0 && a.quad_order && c->d_tail_start.p && quad_positions(a.width, a.rows_local) > 0)
+                                   ? c->d_tail_start.as<unsigned int>() : nullptr;
+    if (tail && !c->tail_stream) {
+        int least = 0, greatest = 0;
+        PTMI_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        PTMI_HIP(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, least));
+        PTMI_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        PTMI_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    it.tail_start = tail;
+    PTMI_HIP(c, launch_streams_advance_missed(a, hits, n_spp, tail, c->stream));
+    PTMI_HIP(c, hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream));
+    if (tail) {
+        PTMI_HIP(c, hipEventRecord(c->ev_fork, c->stream));
+        PTMI_HIP(c, hipStreamWaitEvent(c->tail_stream, c->ev_fork, 0));
     }
 
-    // ---- rays may split, or the samples of a pixel run as unordered items
+    if (passes > 1) {
+        const size_t done_bytes = (size_t)n_regions * sizeof(unsigned int);
+        if (int rc = grow(c, c->d_region_done, done_bytes, "the ordered passes' region counts")) return rc;
+        PTMI_HIP(c, hipMemsetAsync(c->d_region_done.p, 0, done_bytes, c->stream));
+        it.region_done = c->d_region_done.as<unsigned int>();
+    }
+    unsigned int grid = grid_full;
+    const unsigned long long tickets = (unsigned long long)n_regions * (unsigned long long)passes;
+    if (grid > tickets) grid = (unsigned int)(tickets < 1 ? 1 : tickets);
+    PTMI_HIP(c, launch_streams_pixels(a, it, grid, c->stream));
+    if (tail) {
+        PTMI_HIP(c, launch_render_streams_tail(a, tail, c->tail_stream));
+        PTMI_HIP(c, hipEventRecord(c->ev_join, c->tail_stream));
+        PTMI_HIP(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    }
+    return PTMI_OK;
+}
+
+// ---- rays may split, or the samples of a pixel run as unordered items: everything the split kernel's launch needs but for what the
+// overflow levels and a redo change -- passes, snapshots, streams, spill queues, tables, seeds, and the colour backup
+int StreamCall::split_setup()
+{
     if (quad_positions(a.width, a.rows_local) > (1u << 21)) a.quad_cost = nullptr;      // (the item record keeps the quad in 21 bits: no costs beyond 2^29 pixels)
-    unsigned int grid = (unsigned int)(cus * 4 * streams_split_waves());
+    grid = (unsigned int)(cus * 4 * streams_split_waves());
     // the passes: graded items, long first and short ones last (stream_schedule above); PTMI_OPT_STREAM_BATCH caps an item's samples
     int first[kMaxStreamPasses + 1];
     int passes = stream_schedule(n_spp, n, 64ull * grid, c->opt_batch, c->opt_graded != 0, first);
@@ -575,41 +628,24 @@ int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_c
     const unsigned long long n_tickets = (unsigned long long)n_regions * (unsigned long long)passes;      // a ticket = a region of the start-hit list in one pass
     if (n_tickets > 0x7fffffffull) return fail(c, PTMI_ELIMIT, "too many items for the stream form of Streams");
     if (grid > n_tickets) grid = (unsigned int)n_tickets;
-    const size_t snap_bytes = (size_t)passes * hit_slots * sizeof(uint4);
-    if (snap_bytes > c->snapshot_bytes) {
-        PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_snapshots) { (void)hipFree(c->d_snapshots); c->d_snapshots = nullptr; c->snapshot_bytes = 0; }
-        PTMI_HIP(c, hipMalloc(&c->d_snapshots, snap_bytes));
-        c->snapshot_bytes = snap_bytes;
-    }
+    if (int rc = grow(c, c->d_snapshots, (size_t)passes * hit_slots * sizeof(uint4), "the seed snapshots")) return rc;
     // the overflow streams: rays per pixel (PTMI_OPT_STREAM_CAPACITY, or what an earlier call grew them to) x pixels, at least every wave's static block
-    const unsigned int first_block = streams_first_block();
-    const unsigned int level_grid_max = (unsigned int)(cus * 4 * 6);
-    const size_t floor_slots = (size_t)(grid > level_grid_max ? grid : level_grid_max) * first_block + 256;
-    int cap_rays = c->grown_capacity > c->opt_capacity ? c->grown_capacity : c->opt_capacity;
-    auto size_streams = [&](int rays_per_pixel) -> int {
-        size_t need = n * (size_t)rays_per_pixel;
-        if (need < floor_slots) need = floor_slots;
-        if (need > 0xfffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");
-        if (need > c->queue_capacity) {
-            PTMI_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->queue_block) { (void)hipFree(c->queue_block); c->queue_block = nullptr; c->queue_capacity = 0; }
-            PTMI_HIP(c, hipMalloc(&c->queue_block, 2 * (size_t)kRayQueueWords * need * 4));
-            c->queue_capacity = need;
-        }
-        return PTMI_OK;
-    };
-    if (int rc = size_streams(cap_rays)) return rc;
-    size_t capacity = c->queue_capacity;
-    RayQueue q[2] = {carve_queue(c->queue_block, capacity, 0), carve_queue(c->queue_block, capacity, 1)};
-    const size_t spill_records = (size_t)grid * streams_spill_records();
-    if (spill_records > c->spill_capacity) {
-        PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->spill_block) { (void)hipFree(c->spill_block); c->spill_block = nullptr; c->spill_capacity = 0; }
-        PTMI_HIP(c, hipMalloc(&c->spill_block, (size_t)kRayQueueWords * spill_records * 4));
-        c->spill_capacity = spill_records;
+    first_block = streams_first_block();
+    level_grid_max = (unsigned int)(cus * 4 * 6);
+    floor_slots = (size_t)(grid > level_grid_max ? grid : level_grid_max) * first_block + 256;
+    cap_rays = c->grown_capacity > c->opt_capacity ? c->grown_capacity : c->opt_capacity;
+    const size_t need = slots_for(cap_rays);
+    if (need > 0xfffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");
+    if (need > c->queue_capacity) {
+        c->queue_capacity = 0;
+        if (int rc = grow(c, c->queue_block, 2 * (size_t)kRayQueueWords * need * 4, "the overflow streams")) return rc;
+        c->queue_capacity = need;
     }
-    std::vector<unsigned int> base((size_t)kLvMaxLevels, 0u);   // per level (mod kLvMaxLevels): where its reserved blocks start
+    capacity = c->queue_capacity;
+    q[0] = carve_queue(c->queue_block.p, capacity, 0); q[1] = carve_queue(c->queue_block.p, capacity, 1);
+    const size_t spill_records = (size_t)grid * streams_spill_records();
+    if (int rc = grow(c, c->spill_block, (size_t)kRayQueueWords * spill_records * 4, "the spill queues")) return rc;
+    base.assign((size_t)kLvMaxLevels, 0u);
 
     int group_table[kMaxStreamPasses + 1];
     const int groups = pass_group_table(c->opt_pass_groups, first, passes, group_table);
@@ -617,138 +653,138 @@ int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_c
         std::vector<int> table(first, first + passes + 1);
         table.resize((size_t)kMaxStreamPasses + 1, 0);
         table.insert(table.end(), group_table, group_table + groups + 1);
-        if (!c->d_pass_first) PTMI_HIP(c, hipMalloc(&c->d_pass_first, 2 * (size_t)(kMaxStreamPasses + 1) * sizeof(int)));
+        if (int rc = grow(c, c->d_pass_first, 2 * (size_t)(kMaxStreamPasses + 1) * sizeof(int), "the pass tables")) return rc;
         if (table != c->pass_first_host) {
             PTMI_HIP(c, hipStreamSynchronize(c->stream));      // (an earlier launch may still be reading the old tables)
-            PTMI_HIP(c, hipMemcpy(c->d_pass_first, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice));
+            PTMI_HIP(c, hipMemcpy(c->d_pass_first.p, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice));
             c->pass_first_host = table;
         }
     }
-    PTMI_HIP(c, launch_streams_seeds(a.planes, hits, static_cast<uint4 *>(c->d_snapshots), (long long)n, passes, c->d_pass_first, n_spp, c->stream));
-    it.passes = passes; it.pass_first = c->d_pass_first;
-    it.group_first = groups < passes ? c->d_pass_first + (kMaxStreamPasses + 1) : nullptr;     // (every pass on its own needs no table)
+    const int *pass_first = c->d_pass_first.as<int>();
+    PTMI_HIP(c, launch_streams_seeds(a.planes, hits, c->d_snapshots.as<uint4>(), (long long)n, passes, pass_first, n_spp, c->stream));
+    it.passes = passes; it.pass_first = pass_first;
+    it.group_first = groups < passes ? pass_first + (kMaxStreamPasses + 1) : nullptr;     // (every pass on its own needs no table)
     it.groups = groups;
     // GLASS hits wait in their lanes until that many are pending in the wave (measured: DESIGN.md 5.5); nothing to wait for without GLASS
     it.glass_batch = !c->has_glass ? 0 : (c->opt_glass_batch > 0 ? c->opt_glass_batch : kGlassBatchDefault);
-    it.chunk_cursor = tickets_of(0);
-    it.seed_snapshots = static_cast<const uint4 *>(c->d_snapshots);
-    it.spill = carve_queue(c->spill_block, c->spill_capacity, 0);
-    it.out_count = c->d_qcount + cursor_of(0);
+    it.seed_snapshots = c->d_snapshots.as<const uint4>();
+    it.spill = carve_queue(c->spill_block.p, c->spill_block.bytes / ((size_t)kRayQueueWords * 4), 0);
+    it.out_count = qcount() + cursor_of(0);
     it.out_base = grid * first_block;
     it.emitted = it.out_count + 2 * kCounterStride;
     it.may_emit = c->has_glass ? 1 : 0;
 
-    std::vector<unsigned int> raw((size_t)kLvWords);
-    auto emitted_of = [&](int level) {                        // children the level stored: the sum of its shards (read back into `raw`)
-        unsigned long long total = 0;
-        for (int k = 0; k < kLvEmitShards; ++k) total += raw[cursor_of(level) + (size_t)(2 + k) * kCounterStride];
-        return total;
-    };
-    auto read_counters = [&](int levels) -> int {           // the statistics and the lines of the first `levels` levels
-        int lines = kLvCursor + kLvPerLevel * levels;
-        if (lines > kLvTickets) lines = kLvTickets;
-        PTMI_HIP(c, hipMemcpyAsync(raw.data(), c->d_qcount, (size_t)lines * kCounterStride * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        return PTMI_OK;
-    };
     // `expand` (Trace.hs:284-293) makes its vectors as long as the step needs; the overflow streams here have a capacity.  A call that WOULD drop
     // children is therefore redone with longer streams: the three colour planes -- all a launch changes that the next attempt reads; the seeds moved
     // before the launch, the snapshots stand -- are copied aside first (25 MB at 1080p: ~ 10 us in stream order), and when the counters say that
     // children found no room the planes are put back, the streams doubled (up to kMaxStreamRaysPerPixel rays per pixel, or to what the device
     // still has) and the launch and its levels run again.  The capacity a call reached is kept for later calls.  Only with GLASS: nothing else emits.
-    const size_t plane_bytes = n * sizeof(float);
+    plane_bytes = n * sizeof(float);
     // (only while a redo is possible: with the streams at kMaxStreamRaysPerPixel already the drops would stand, and nothing is copied aside.
     // The recorded quad costs of the launch are part of what a redo must take back: the failed attempt's items added theirs.)
-    const size_t cost_bytes = a.quad_cost ? (size_t)quad_positions(a.width, a.rows_local) * sizeof(unsigned int) : 0;
-    const bool can_redo = c->has_glass && cap_rays < kMaxStreamRaysPerPixel;
+    cost_bytes = a.quad_cost ? (size_t)quad_positions(a.width, a.rows_local) * sizeof(unsigned int) : 0;
+    can_redo = c->has_glass && cap_rays < kMaxStreamRaysPerPixel;
     if (can_redo) {
-        if (3 * plane_bytes + cost_bytes > c->colour_backup_bytes) {
-            PTMI_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->colour_backup) { (void)hipFree(c->colour_backup); c->colour_backup = nullptr; c->colour_backup_bytes = 0; }
-            PTMI_HIP(c, hipMalloc(&c->colour_backup, 3 * plane_bytes + cost_bytes));
-            c->colour_backup_bytes = 3 * plane_bytes + cost_bytes;
-        }
-        char *bk = static_cast<char *>(c->colour_backup);
-        PTMI_HIP(c, hipMemcpyAsync(bk, a.planes.r, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        PTMI_HIP(c, hipMemcpyAsync(bk + plane_bytes, a.planes.g, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        PTMI_HIP(c, hipMemcpyAsync(bk + 2 * plane_bytes, a.planes.b, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        if (cost_bytes) PTMI_HIP(c, hipMemcpyAsync(bk + 3 * plane_bytes, a.quad_cost, cost_bytes, hipMemcpyDeviceToDevice, c->stream));
-    } else if (c->colour_backup && !c->has_glass) {          // the scene lost its GLASS: the three planes' worth of memory goes back
+        if (int rc = grow(c, c->colour_backup, 3 * plane_bytes + cost_bytes, "the colour backup")) return rc;
+        return copy_colour(false);
+    }
+    if (c->colour_backup.p && !c->has_glass) {             // the scene lost its GLASS: the three planes' worth of memory goes back
         PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->colour_backup); c->colour_backup = nullptr; c->colour_backup_bytes = 0;
+        release(c->colour_backup);
     }
-    unsigned long long overflowed = 0;
-    for (int attempt = 0;; ++attempt) {
-        it.out = q[0];
-        base[0] = it.out_base;
-        PTMI_HIP(c, launch_streams_split(a, it, grid, c->stream));
-        // stream_iterations lives in the per-pixel kernels' sharded counter: shard 0 carries this form's figure, copied on the device
-        if (attempt == 0) PTMI_HIP(c, hipMemsetAsync(c->d_iters, 0, kItersBytes, c->stream));
-        if (int rc = read_counters(1)) return rc;
-        overflowed = 0;
-        // `null state` (Trace.hs:166-170): the loop goes on while the last level left children in its overflow stream (a level
-        // cuts the rays the step cap forbids as it reads them, and counts them)
-        for (int level = 0; c->has_glass && emitted_of(level) > 0u;) {
-            overflowed += emitted_of(level);
-            const size_t cursor = (size_t)raw[cursor_of(level)] + base[(size_t)(level % kLvMaxLevels)];
-            const size_t items = cursor < capacity ? cursor : capacity;
-            ++level;
-            LevelArgs lv{};
-            lv.in = q[(level + 1) & 1]; lv.out = q[level & 1];
-            lv.stats = c->d_qcount;
-            lv.in_count = c->d_qcount + cursor_of(level - 1);
-            lv.in_base = base[(size_t)((level - 1) % kLvMaxLevels)];
-            lv.out_count = c->d_qcount + cursor_of(level);
-            lv.emitted = lv.out_count + 2 * kCounterStride;
-            lv.may_emit = 1;
-            const size_t chunks = (items + 63) / 64;
-            const unsigned int lgrid = (unsigned int)(chunks < 1 ? 1 : (chunks > level_grid_max ? level_grid_max : chunks));
-            lv.out_base = lgrid * first_block;
-            base[(size_t)(level % kLvMaxLevels)] = lv.out_base;
-            // the counter words of this level: long idle when they come round again
-            PTMI_HIP(c, hipMemsetAsync(lv.out_count, 0, (size_t)kLvPerLevel * kCounterStride * sizeof(unsigned int), c->stream));
-            PTMI_HIP(c, launch_streams_level(a, lv, lgrid, c->stream));
-            if (int rc = read_counters(level + 1)) return rc;
-        }
-        const unsigned int dropped = raw[(size_t)kLvDropped * kCounterStride];
-        if (!can_redo || dropped == 0u || cap_rays >= kMaxStreamRaysPerPixel) break;
-        // ---- children were dropped: longer streams, the planes put back, once more.  "Longer" must be true: the block may be larger than
-        // rays-per-pixel x pixels says (the floor of the waves' static blocks, a block left over from a larger image, a lowered
-        // PTMI_OPT_STREAM_CAPACITY), and a redo into streams of the same length drops the same children again -- so the capacity doubles until
-        // it asks for more than is there; if even kMaxStreamRaysPerPixel does not, the drops stand, counted.
-        int grown = cap_rays;
-        size_t need = 0;
-        do {
-            grown = grown * 2 < kMaxStreamRaysPerPixel ? grown * 2 : kMaxStreamRaysPerPixel;
-            need = n * (size_t)grown;
-            if (need < floor_slots) need = floor_slots;
-        } while (need <= capacity && grown < kMaxStreamRaysPerPixel);
-        if (need <= capacity) { c->grown_capacity = grown; break; }
-        if (need > 0xfffffff0ull) break;
-        if (need > c->queue_capacity) {
-            void *bigger = nullptr;
-            if (hipMalloc(&bigger, 2 * (size_t)kRayQueueWords * need * 4) != hipSuccess) { (void)hipGetLastError(); break; }    // the device has no more: the drops stand, counted
-            (void)hipFree(c->queue_block);                   // (the stream is idle: read_counters synchronised it)
-            c->queue_block = bigger; c->queue_capacity = need;
-        }
-        cap_rays = grown; c->grown_capacity = grown;
-        capacity = c->queue_capacity;
-        q[0] = carve_queue(c->queue_block, capacity, 0); q[1] = carve_queue(c->queue_block, capacity, 1);
-        char *bk = static_cast<char *>(c->colour_backup);
-        PTMI_HIP(c, hipMemcpyAsync(a.planes.r, bk, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        PTMI_HIP(c, hipMemcpyAsync(a.planes.g, bk + plane_bytes, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        PTMI_HIP(c, hipMemcpyAsync(a.planes.b, bk + 2 * plane_bytes, plane_bytes, hipMemcpyDeviceToDevice, c->stream));
-        if (cost_bytes) PTMI_HIP(c, hipMemcpyAsync(a.quad_cost, bk + 3 * plane_bytes, cost_bytes, hipMemcpyDeviceToDevice, c->stream));
-        // every counter of the call starts over -- but for the split pixels' count, which the primary kernel wrote and which is not run again
-        const unsigned int split_pixels = raw[(size_t)kLvSplitPixels * kCounterStride];
-        PTMI_HIP(c, hipMemsetAsync(c->d_qcount, 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
-        PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_qcount + (size_t)kLvSplitPixels * kCounterStride), (int)split_pixels, 1, c->stream));
-        std::fill(base.begin(), base.end(), 0u);
+    return PTMI_OK;
+}
+
+// the three colour planes and the launch's recorded quad costs into the colour backup, or back from it
+int StreamCall::copy_colour(bool restore)
+{
+    void *dev[4] = {a.planes.r, a.planes.g, a.planes.b, a.quad_cost};
+    for (int i = 0; i < 4; ++i) {
+        const size_t bytes = i < 3 ? plane_bytes : cost_bytes;
+        char *kept = c->colour_backup.as<char>() + (size_t)i * plane_bytes;
+        if (bytes) PTMI_HIP(c, hipMemcpyAsync(restore ? dev[i] : kept, restore ? kept : dev[i], bytes, hipMemcpyDeviceToDevice, c->stream));
     }
+    return PTMI_OK;
+}
+
+int StreamCall::read_counters(int levels)                // the statistics and the lines of the first `levels` levels
+{
+    int lines = kLvCursor + kLvPerLevel * levels;
+    if (lines > kLvTickets) lines = kLvTickets;
+    PTMI_HIP(c, hipMemcpyAsync(raw.data(), qcount(), (size_t)lines * kCounterStride * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
+}
+
+// `null state` (Trace.hs:166-170): the loop goes on while the last level left children in its overflow stream (a level
+// cuts the rays the step cap forbids as it reads them, and counts them)
+int StreamCall::overflow_levels(unsigned long long &overflowed)
+{
+    overflowed = 0;
+    for (int level = 0; c->has_glass && emitted_of(level) > 0u;) {
+        overflowed += emitted_of(level);
+        const size_t cursor = (size_t)raw[cursor_of(level)] + base[(size_t)(level % kLvMaxLevels)];
+        const size_t items = cursor < capacity ? cursor : capacity;
+        ++level;
+        LevelArgs lv{};
+        lv.in = q[(level + 1) & 1]; lv.out = q[level & 1];
+        lv.stats = qcount();
+        lv.in_count = qcount() + cursor_of(level - 1);
+        lv.in_base = base[(size_t)((level - 1) % kLvMaxLevels)];
+        lv.out_count = qcount() + cursor_of(level);
+        lv.emitted = lv.out_count + 2 * kCounterStride;
+        lv.may_emit = 1;
+        const size_t chunks = (items + 63) / 64;
+        const unsigned int lgrid = (unsigned int)(chunks < 1 ? 1 : (chunks > level_grid_max ? level_grid_max : chunks));
+        lv.out_base = lgrid * first_block;
+        base[(size_t)(level % kLvMaxLevels)] = lv.out_base;
+        // the counter words of this level: long idle when they come round again
+        PTMI_HIP(c, hipMemsetAsync(lv.out_count, 0, (size_t)kLvPerLevel * kCounterStride * sizeof(unsigned int), c->stream));
+        PTMI_HIP(c, launch_streams_level(a, lv, lgrid, c->stream));
+        if (int rc = read_counters(level + 1)) return rc;
+    }
+    return PTMI_OK;
+}
+
+// ---- children were dropped: longer streams, the planes put back, once more.  "Longer" must be true: the block may be larger than
+// rays-per-pixel x pixels says (the floor of the waves' static blocks, a block left over from a larger image, a lowered
+// PTMI_OPT_STREAM_CAPACITY), and a redo into streams of the same length drops the same children again -- so the capacity doubles until
+// it asks for more than is there; if even kMaxStreamRaysPerPixel does not, the drops stand, counted.  *again: the launch runs once more.
+int StreamCall::redo_longer(bool *again)
+{
+    *again = false;
+    int grown = cap_rays;
+    size_t need = 0;
+    do {
+        grown = grown * 2 < kMaxStreamRaysPerPixel ? grown * 2 : kMaxStreamRaysPerPixel;
+        need = slots_for(grown);
+    } while (need <= capacity && grown < kMaxStreamRaysPerPixel);
+    if (need <= capacity) { c->grown_capacity = grown; return PTMI_OK; }
+    if (need > 0xfffffff0ull) return PTMI_OK;
+    DeviceBlock bigger;                                    // (first: if the device has no more, the old streams stay and the drops stand, counted)
+    if (allocate(bigger, 2 * (size_t)kRayQueueWords * need * 4) != hipSuccess) return PTMI_OK;
+    release(c->queue_block);                               // (the stream is idle: read_counters synchronised it)
+    c->queue_block = bigger; c->queue_capacity = need;
+    cap_rays = grown; c->grown_capacity = grown;
+    capacity = need;
+    q[0] = carve_queue(c->queue_block.p, capacity, 0); q[1] = carve_queue(c->queue_block.p, capacity, 1);
+    if (int rc = copy_colour(true)) return rc;
+    // every counter of the call starts over -- but for the split pixels' count, which the primary kernel wrote and which is not run again
+    const unsigned int split_pixels = raw[(size_t)kLvSplitPixels * kCounterStride];
+    PTMI_HIP(c, hipMemsetAsync(qcount(), 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(qcount() + (size_t)kLvSplitPixels * kCounterStride), (int)split_pixels, 1, c->stream));
+    std::fill(base.begin(), base.end(), 0u);
+    *again = true;
+    return PTMI_OK;
+}
+
+// the counters read back after the last level, folded into the context's statistics
+int StreamCall::fold_counters(unsigned long long overflowed)
+{
     c->rays_overflowed += overflowed;
     for (int k = 0; k < kLvLiveShards; ++k) c->live_host += raw[(size_t)(kLvLive + k) * kCounterStride];
     // the two children of every glass primary hit whose split is cached in the start list: counted here, per sample
-    if (!list_kept) c->hit_split_pixels = raw[(size_t)kLvSplitPixels * kCounterStride];
+    if (fresh_list) c->hit_split_pixels = raw[(size_t)kLvSplitPixels * kCounterStride];
     c->live_host += 2ull * c->hit_split_pixels * (uint64_t)n_spp;
     c->rays_dropped += raw[(size_t)kLvDropped * kCounterStride];
     c->rays_truncated += raw[(size_t)kLvCut * kCounterStride];
@@ -756,9 +792,58 @@ int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_c
     unsigned int longest = raw[(size_t)kLvDeepest * kCounterStride];            // stream_iterations: the deepest step of this call
     if (c->hit_split_pixels && longest < 2) longest = 2;                        // the children of the cached glass primary hits: traceStep 2
     if (longest == 0) longest = 1;                                              // every primary ray missed: one traceStep all the same
-    PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_iters), (int)longest, 1, c->stream));
-    guard.done = true;
+    PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_iters.p), (int)longest, 1, c->stream));
     return PTMI_OK;
+}
+
+int split_passes(StreamCall &s)
+{
+    if (int rc = s.split_setup()) return rc;
+    s.raw.assign((size_t)kLvWords, 0u);
+    unsigned long long overflowed = 0;
+    for (int attempt = 0;; ++attempt) {
+        s.it.out = s.q[0];
+        s.base[0] = s.it.out_base;
+        PTMI_HIP(s.c, launch_streams_split(s.a, s.it, s.grid, s.c->stream));
+        // stream_iterations lives in the per-pixel kernels' sharded counter: shard 0 carries this form's figure, copied on the device
+        if (attempt == 0) PTMI_HIP(s.c, hipMemsetAsync(s.c->d_iters.p, 0, kItersBytes, s.c->stream));
+        if (int rc = s.read_counters(1)) return rc;
+        if (int rc = s.overflow_levels(overflowed)) return rc;
+        const unsigned int dropped = s.raw[(size_t)kLvDropped * kCounterStride];
+        if (!s.can_redo || dropped == 0u || s.cap_rays >= kMaxStreamRaysPerPixel) break;
+        bool again = false;
+        if (int rc = s.redo_longer(&again)) return rc;
+        if (!again) break;
+    }
+    return s.fold_counters(overflowed);
+}
+
+int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_camera &camera)
+{
+    const size_t n = (size_t)a.rows_local * a.width;
+    if (n == 0 || n_spp <= 0) return PTMI_OK;
+    if (n > 0x3ffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");   // 32-bit byte offsets into the planes
+    const bool ordered = !c->has_glass && (c->opt_batch == 0 || a.seed_from_result);
+    const unsigned int n_regions = streams_regions(a.width, a.rows_local);
+    const unsigned int region_slots = ordered ? 64u : 128u;    // a glass primary hit contributes up to two start hits
+    const size_t hit_slots = (size_t)n_regions * region_slots;
+    if (hit_slots > 0xfffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");
+    StreamCall s{c, a, n_spp, n, n_regions, region_slots, hit_slots, c->cus > 0 ? c->cus : 256};
+    int rc = s.start_hit_list(camera);
+    if (rc == PTMI_OK) {
+        ItemArgs &it = s.it;
+        it.hits = s.hits;
+        it.n_positions = n_regions / 4u;
+        it.passes = 1; it.group_first = nullptr; it.groups = 0;
+        it.n_slots = (unsigned int)hit_slots;
+        it.stats = s.qcount();
+        it.chunk_cursor = s.qcount() + (size_t)kLvTickets * kCounterStride;
+        rc = ordered ? s.ordered_passes() : split_passes(s);
+    }
+    // A list built by THIS call counts as kept by later ones only if this call gets to its end: what the host keeps beside it (the split pixels'
+    // count, read back by the split kernel's steps) is only then the list's.  Any error return on the way leaves the list invalid.
+    if (rc != PTMI_OK && s.fresh_list) c->hit_list_valid = false;
+    return rc;
 }
 
 int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, int algorithm,
@@ -767,16 +852,16 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
 {
     RenderArgs a{};
     a.cam = make_uniforms(*camera, width, height);
-    a.scene.packed = c->d_scene; a.scene.n_spheres = c->n_spheres; a.scene.n_planes = c->n_planes;
+    a.scene.packed = c->d_scene.as<float4>(); a.scene.n_spheres = c->n_spheres; a.scene.n_planes = c->n_planes;
     a.planes = planes;
     a.screen_x = sx; a.screen_y = sy;
     a.width = width; a.height = height; a.rows_local = rows_local;
     a.stripe_rows = stripe_rows; a.n_parts = n_parts; a.part = part;
     a.bounce_limit = bounce_limit; a.n_spp = n_spp;
     a.cus = c->cus;
-    a.live_counter = c->d_live; a.work_counter = c->d_work; a.stream_iterations = c->d_iters;
+    a.live_counter = c->d_live.as<unsigned long long>(); a.work_counter = c->d_work.as<unsigned int>(); a.stream_iterations = c->d_iters.as<unsigned int>();
     a.stream_step_cap = c->opt_step_cap; a.seed_from_result = effective_seed_rule(c) == PTMI_SEED_FROM_RESULT;
-    a.stream_counters = c->d_stream_counters;
+    a.stream_counters = c->d_stream_counters.as<unsigned long long>();
     const bool stream_form = uses_stream_form(c, algorithm, n_parts, n_spp);
     // Cost-ordered dispatch (ptmi_device.h: lane_pixel): launches with one (camera, scene, shape, limit, algorithm)
     // record what every quad of tiles costs; later launches with the same key dispatch the most expensive quads first
@@ -791,13 +876,12 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
 #endif
     if (stream_form ? stream_order : uses_quad_order(a, algorithm == PTMI_INLINE, c->variant)) {
         const unsigned int n_quads = quad_positions(width, rows_local);
-        if (n_quads > c->quad_capacity) {
-            if (c->d_quad_cost) { PTMI_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_quad_cost); (void)hipFree(c->d_quad_order); (void)hipFree(c->d_quad_class); }
-            c->d_quad_cost = c->d_quad_order = c->d_quad_class = nullptr; c->quad_capacity = 0; c->order_state = 0; ++c->order_generation;
-            PTMI_HIP(c, hipMalloc(&c->d_quad_cost, n_quads * sizeof(unsigned int)));
-            PTMI_HIP(c, hipMalloc(&c->d_quad_order, n_quads * sizeof(unsigned int)));
-            PTMI_HIP(c, hipMalloc(&c->d_quad_class, n_quads * sizeof(unsigned int)));
-            c->quad_capacity = n_quads;
+        const size_t quad_bytes = n_quads * sizeof(unsigned int);
+        DeviceBlock *quads[3] = {&c->d_quad_cost, &c->d_quad_order, &c->d_quad_class};
+        if (std::any_of(quads, quads + 3, [&](const DeviceBlock *q) { return q->bytes < quad_bytes; })) {
+            c->order_state = 0; ++c->order_generation;
+            for (DeviceBlock *q : quads)
+                if (int rc = grow(c, *q, quad_bytes, "the dispatch order")) return rc;
         }
         ptmi_ctx::OrderKey key{};
         key.cam = *camera; key.scene_version = c->scene_version;
@@ -809,10 +893,10 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
         const int launches = c->order_state;
         int rebuild = 0, record = 0;
         const int state_after = order_schedule(launches, stream_form ? 1 : 0, &rebuild, &record);
-        if (!c->d_tail_start) PTMI_HIP(c, hipMalloc(&c->d_tail_start, 64));
+        if (int rc = grow(c, c->d_tail_start, 64, "the tail's start")) return rc;
         if (launches == 0) {
-            PTMI_HIP(c, hipMemsetAsync(c->d_quad_cost, 0, n_quads * sizeof(unsigned int), c->stream));
-            PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_tail_start), (int)n_quads, 1, c->stream));   // no tail yet
+            PTMI_HIP(c, hipMemsetAsync(c->d_quad_cost.p, 0, quad_bytes, c->stream));
+            PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_tail_start.p), (int)n_quads, 1, c->stream));   // no tail yet
         } else if (rebuild) {
             // (the stream form: the order kernel also says where the order's cheap end begins -- render_streams_wavefront.  How much of the
             // recorded cost that end may hold: 15 % where a lane sees four pixels or more, 40 % where it sees fewer -- 1280x720 / 64 spp: 2.34 ms
@@ -820,23 +904,23 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
             const unsigned long long lanes_full = 64ull * (unsigned long long)(c->cus > 0 ? c->cus : 256) * 4ull * (unsigned long long)streams_pixels_waves();
             const unsigned int tail_permille = c->opt_tail_permille >= 0 ? (unsigned int)c->opt_tail_permille
                                              : ((unsigned long long)width * (unsigned long long)rows_local < 4ull * lanes_full ? 400u : 150u);
-            PTMI_HIP(c, launch_quad_order(c->d_quad_cost, c->d_quad_order, c->d_quad_class, n_quads, stream_form ? c->d_tail_start : nullptr,
-                                          tail_permille, c->stream));
+            PTMI_HIP(c, launch_quad_order(c->d_quad_cost.as<unsigned int>(), c->d_quad_order.as<unsigned int>(), c->d_quad_class.as<unsigned int>(), n_quads,
+                                          stream_form ? c->d_tail_start.as<unsigned int>() : nullptr, tail_permille, c->stream));
             ++c->order_generation;
         }
-        if (launches > 0) a.quad_order = c->d_quad_order;
-        if (record) a.quad_cost = c->d_quad_cost;
+        if (launches > 0) a.quad_order = c->d_quad_order.as<unsigned int>();
+        if (record) a.quad_cost = c->d_quad_cost.as<unsigned int>();
         next_order_state = state_after;                        // (every launch counts, whether or not it records)
     }
     if (per_pixel_kernel) {
         // one word per tile workgroup for the sample chunks of the tiled per-pixel kernels (ptmi_device.h: enter_sample_chunk)
         const unsigned int need = ((unsigned int)(((width + 7) / 8) * ((rows_local + 7) / 8)) + 31u) & ~31u;
         if (need > c->chunk_capacity) {
-            if (c->d_chunk_done) { PTMI_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_chunk_done); c->d_chunk_done = nullptr; c->chunk_capacity = 0; }
-            PTMI_HIP(c, hipMalloc(&c->d_chunk_done, ((size_t)need + 32) * sizeof(unsigned int)));     // + the ticket counter's line
+            c->chunk_capacity = 0;
+            if (int rc = grow(c, c->d_chunk_done, ((size_t)need + 32) * sizeof(unsigned int), "the sample chunks")) return rc;     // + the ticket counter's line
             c->chunk_capacity = need;
         }
-        a.chunk_done = c->d_chunk_done; a.chunk_capacity = c->chunk_capacity;
+        a.chunk_done = c->d_chunk_done.as<unsigned int>(); a.chunk_capacity = c->chunk_capacity;
         a.spp_chunks = sx ? 1 : c->opt_spp_chunks;
     }
     if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev0, c->stream)); }
@@ -849,16 +933,8 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
     } else if (c->has_glass) {                             // rays may split: the per-pixel tree walk
         // the first waiting children of every lane as 64-byte records in global memory (ptmi_streams_tree.hip): 16 KB per tile
         const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
-        if (want > c->tree_stack_bytes) {
-            PTMI_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->tree_stack) { (void)hipFree(c->tree_stack); c->tree_stack = nullptr; c->tree_stack_bytes = 0; }
-            if (hipMalloc(&c->tree_stack, want) != hipSuccess) {
-                (void)hipGetLastError(); c->tree_stack = nullptr;
-                return fail(c, PTMI_ENOMEM, "no device memory for the tree walk's records of waiting children (16 KB per 8x8 tile)");
-            }
-            c->tree_stack_bytes = want;
-        }
-        a.tree_stack = static_cast<float4 *>(c->tree_stack);
+        if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
+        a.tree_stack = c->tree_stack.as<float4>();
         PTMI_HIP(c, launch_render_streams_tree(a, c->variant, c->stream));
     } else {
         PTMI_HIP(c, launch_render_streams(a, c->variant, c->stream));
@@ -878,7 +954,7 @@ int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int
     if (algorithm != PTMI_INLINE && algorithm != PTMI_STREAMS) return fail(c, PTMI_EINVAL, "unknown algorithm");
     if (bounce_limit < 0) return fail(c, PTMI_EINVAL, "bounce_limit < 0");
     if (n_spp < 0) return fail(c, PTMI_EINVAL, "n_spp < 0");
-    if (!c->d_scene) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (!c->d_scene.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     // "features that require diverging rays like light refraction" need the stream algorithm (Trace.hs:56-67)
     if (algorithm == PTMI_INLINE && c->has_glass)
         return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
@@ -1110,15 +1186,15 @@ int ptmi_create(ptmi_ctx **out, int device)
     if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipEventCreateWithFlags(&c->ev_snap, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipMalloc(&c->d_live, kLiveBytes)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&c->d_work, kWorkWords * sizeof(unsigned int))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&c->d_iters, kItersBytes)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&c->d_stream_counters, kScWords * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemsetAsync(c->d_stream_counters, 0, kScWords * sizeof(unsigned long long), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    if ((e = allocate(c->d_live, kLiveBytes)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = allocate(c->d_work, kWorkWords * sizeof(unsigned int))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = allocate(c->d_iters, kItersBytes)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = allocate(c->d_stream_counters, kScWords * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = hipMemsetAsync(c->d_stream_counters.p, 0, kScWords * sizeof(unsigned long long), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
     // stream-ordered fills: the context's stream is non-blocking, so a NULL-stream hipMemset would race with it
-    if ((e = hipMemsetAsync(c->d_live, 0, kLiveBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    if ((e = hipMemsetAsync(c->d_work, 0, kWorkWords * sizeof(unsigned int), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    if ((e = hipMemsetAsync(c->d_iters, 0, kItersBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(c->d_live.p, 0, kLiveBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(c->d_work.p, 0, kWorkWords * sizeof(unsigned int), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
     *out = c;
     return PTMI_OK;
@@ -1129,35 +1205,13 @@ void ptmi_destroy(ptmi_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    if (c->owned_block) (void)hipFree(c->owned_block);
-    if (c->d_scene) (void)hipFree(c->d_scene);
-    if (c->d_live) (void)hipFree(c->d_live);
-    if (c->d_work) (void)hipFree(c->d_work);
-    if (c->d_pass_first) (void)hipFree(c->d_pass_first);
-    if (c->d_iters) (void)hipFree(c->d_iters);
-    if (c->d_stream_counters) (void)hipFree(c->d_stream_counters);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->queue_block) (void)hipFree(c->queue_block);
-    if (c->colour_backup) (void)hipFree(c->colour_backup);
-    if (c->hit_block) (void)hipFree(c->hit_block);
-    if (c->d_hit_counts) (void)hipFree(c->d_hit_counts);
-    if (c->d_hit_missed) (void)hipFree(c->d_hit_missed);
-    if (c->d_snapshots) (void)hipFree(c->d_snapshots);
-    if (c->spill_block) (void)hipFree(c->spill_block);
-    if (c->tree_stack) (void)hipFree(c->tree_stack);
-    if (c->d_qcount) (void)hipFree(c->d_qcount);
-    if (c->d_quad_cost) (void)hipFree(c->d_quad_cost);
-    if (c->d_quad_order) (void)hipFree(c->d_quad_order);
-    if (c->d_quad_class) (void)hipFree(c->d_quad_class);
-    if (c->d_tail_start) (void)hipFree(c->d_tail_start);
+    c->each_block([](DeviceBlock &b) { release(b); });
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->tail_stream) { (void)hipStreamSynchronize(c->tail_stream); (void)hipStreamDestroy(c->tail_stream); }
-    if (c->d_chunk_done) (void)hipFree(c->d_chunk_done);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_snap) (void)hipEventDestroy(c->ev_snap);
-    if (c->d_region_done) (void)hipFree(c->d_region_done);
     for (ptmi_ctx::ChainState &st : c->chain) if (st.block) (void)hipFree(st.block);
     for (auto &fb : c->chain_free) (void)hipFree(fb.second);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1185,13 +1239,13 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     pack_scene(spheres, n_spheres, planes, n_planes, packed);
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     // the new scene stands complete before the old one goes: a failure here leaves the context with the scene (and the counts) it had
-    void *fresh = nullptr;
-    PTMI_HIP(c, hipMalloc(&fresh, packed.size() * sizeof(float4)));
-    hipError_t e = hipMemcpyAsync(fresh, packed.data(), packed.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream);
+    DeviceBlock fresh;
+    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
+    hipError_t e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed` dies at return
-    if (e != hipSuccess) { (void)hipFree(fresh); PTMI_HIP(c, e); }
-    if (c->d_scene) (void)hipFree(c->d_scene);
-    c->d_scene = static_cast<float4 *>(fresh);
+    if (e != hipSuccess) { release(fresh); PTMI_HIP(c, e); }
+    release(c->d_scene);
+    c->d_scene = fresh;
     c->n_spheres = n_spheres; c->n_planes = n_planes;
     ++c->scene_version;
     c->has_glass = false;
@@ -1206,7 +1260,7 @@ int ptmi_set_partition(ptmi_ctx *c, int stripe_rows, int n_parts, int part)
     std::lock_guard<std::mutex> lock(c->mu);
     if (stripe_rows <= 0 || n_parts <= 0 || part < 0 || part >= n_parts)
         return fail(c, PTMI_EINVAL, "bad partition");
-    if (c->owned_block) return fail(c, PTMI_ESTATE, "ptmi_set_partition must precede ptmi_resize");
+    if (c->owned_block.p) return fail(c, PTMI_ESTATE, "ptmi_set_partition must precede ptmi_resize");
     c->stripe_rows = stripe_rows; c->n_parts = n_parts; c->part = part;
     return PTMI_OK;
 }
@@ -1219,8 +1273,8 @@ int ptmi_resize(ptmi_ctx *c, int width, int height)
     if (too_many_pixels(width, height)) return fail(c, PTMI_ELIMIT, "image too large");
     PTMI_HIP(c, hipSetDevice(c->device));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->owned_block) { (void)hipFree(c->owned_block); c->owned_block = nullptr; }
-    if (c->colour_backup) { (void)hipFree(c->colour_backup); c->colour_backup = nullptr; c->colour_backup_bytes = 0; }   // (sized by the old image)
+    release(c->owned_block);
+    release(c->colour_backup);                                         // (sized by the old image)
     // The old planes are gone (first: the new ones may need their room).  Until the new ones stand the context is UNSIZED -- a failure below
     // must not leave it pointing into the block just freed: every call that needs planes then answers PTMI_ESTATE.
     c->owned = Planes{};
@@ -1229,13 +1283,13 @@ int ptmi_resize(ptmi_ctx *c, int width, int height)
     const int rows_local = rows_of_part(height, effective_stripe(c), c->n_parts, c->part);
     const size_t n = (size_t)rows_local * (size_t)width;
     const size_t bytes = planes_bytes(n > 0 ? n : 1);
-    void *block = nullptr;
-    PTMI_HIP(c, hipMalloc(&block, bytes));
-    hipError_t e = hipMemsetAsync(block, 0, bytes, c->stream);         // ordered before anything launched on the stream
+    DeviceBlock block;
+    PTMI_HIP(c, allocate(block, bytes));
+    hipError_t e = hipMemsetAsync(block.p, 0, bytes, c->stream);       // ordered before anything launched on the stream
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(block); PTMI_HIP(c, e); }
+    if (e != hipSuccess) { release(block); PTMI_HIP(c, e); }
     c->owned_block = block;
-    c->owned = carve(block, n > 0 ? n : 1);
+    c->owned = carve(block.p, n > 0 ? n : 1);
     c->width = width; c->height = height; c->rows_local = rows_local;
     return PTMI_OK;
 }
@@ -1362,10 +1416,10 @@ int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
     case PTMI_OPT_STREAM_CAPACITY:
         if (value < 1 || value > 64) return fail(c, PTMI_EINVAL, "stream capacity must be in [1, 64] rays per pixel-sample");
         c->opt_capacity = (int)value; c->grown_capacity = 0;
-        if (c->queue_block) {                                // "starts over from the value given": the streams are carved anew by the next call
+        if (c->queue_block.p) {                              // "starts over from the value given": the streams are carved anew by the next call
             PTMI_HIP(c, hipSetDevice(c->device));
             PTMI_HIP(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->queue_block); c->queue_block = nullptr; c->queue_capacity = 0;
+            release(c->queue_block); c->queue_capacity = 0;
         }
         return PTMI_OK;
     case PTMI_OPT_STREAMS_FORM:
@@ -1455,8 +1509,8 @@ int ptmi_create_with(ptmi_ctx *c, const uint32_t *w0, const uint32_t *w1, const 
     if (!w0 || !w1 || !w2) return fail(c, PTMI_EINVAL, "word planes are NULL");
     PTMI_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->rows_local * c->width;
-    if (int rc = ensure_scratch(c, 3 * n * 4)) return rc;
-    uint32_t *d = static_cast<uint32_t *>(c->scratch);
+    if (int rc = grow(c, c->scratch, 3 * n * 4, "scratch")) return rc;
+    uint32_t *d = c->scratch.as<uint32_t>();
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     const CopySpan words[3] = {{d, const_cast<uint32_t *>(w0), n * 4}, {d + n, const_cast<uint32_t *>(w1), n * 4},
                                {d + 2 * n, const_cast<uint32_t *>(w2), n * 4}};
@@ -1565,9 +1619,9 @@ int ptmi_render1(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int boun
     const size_t n = (size_t)width * height;
     const size_t pb = planes_bytes(n);
     const size_t sb = screen_x ? 2 * n * sizeof(int64_t) : 0;
-    if (int rc = ensure_scratch(c, pb + sb)) return rc;
-    Planes p = carve(c->scratch, n);
-    int64_t *dsx = screen_x ? reinterpret_cast<int64_t *>(static_cast<char *>(c->scratch) + pb) : nullptr;
+    if (int rc = grow(c, c->scratch, pb + sb, "scratch")) return rc;
+    Planes p = carve(c->scratch.p, n);
+    int64_t *dsx = screen_x ? reinterpret_cast<int64_t *>(c->scratch.as<char>() + pb) : nullptr;
     int64_t *dsy = screen_x ? dsx + n : nullptr;
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     const void *src[7] = {r_in, g_in, b_in, sa_in, sb_in, sc_in, sctr_in};
@@ -1695,9 +1749,9 @@ int ptmi_present(ptmi_ctx *c, int iterations, float *rgb32f_out, uint8_t *rgba8_
     const size_t n = (size_t)c->rows_local * c->width;
     if (n == 0) return PTMI_OK;
     const size_t rgb_bytes = ((n * 12 + 255) / 256) * 256;
-    if (int rc = ensure_scratch(c, rgb_bytes + n * 4)) return rc;
-    float *d_rgb = static_cast<float *>(c->scratch);
-    uint32_t *d_rgba = reinterpret_cast<uint32_t *>(static_cast<char *>(c->scratch) + rgb_bytes);
+    if (int rc = grow(c, c->scratch, rgb_bytes + n * 4, "scratch")) return rc;
+    float *d_rgb = c->scratch.as<float>();
+    uint32_t *d_rgba = reinterpret_cast<uint32_t *>(c->scratch.as<char>() + rgb_bytes);
     PTMI_HIP(c, launch_present(active(c), (long long)n, iterations, rgb32f_out ? d_rgb : nullptr,
                                rgba8_out ? d_rgba : nullptr, c->stream));
     CopySpan out[2];
@@ -1738,9 +1792,9 @@ int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out)
     unsigned long long live = 0, sc[kScWords] = {0, 0, 0, 0}; unsigned int iters = 0;
     std::vector<unsigned long long> live_shards((size_t)kStatShards * kStatStride);     // the sharded statistics: sum / maximum over the shards
     std::vector<unsigned int> iter_shards((size_t)kStatShards * 2 * kStatStride);
-    PTMI_HIP(c, hipMemcpyAsync(live_shards.data(), c->d_live, kLiveBytes, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(sc, c->d_stream_counters, sizeof sc, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(iter_shards.data(), c->d_iters, kItersBytes, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(live_shards.data(), c->d_live.p, kLiveBytes, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(sc, c->d_stream_counters.p, sizeof sc, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(iter_shards.data(), c->d_iters.p, kItersBytes, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < kStatShards; ++k) {
         live += live_shards[(size_t)k * kStatStride];
@@ -1766,7 +1820,7 @@ int ptmi_debug_counters_n(ptmi_ctx *c, uint32_t *out, int capacity)
     if (capacity < 0) return fail(c, PTMI_EINVAL, "capacity is negative");
     const int words = capacity < kWorkWords ? capacity : kWorkWords;
     PTMI_HIP(c, hipSetDevice(c->device));
-    if (words > 0) PTMI_HIP(c, hipMemcpyAsync(out, c->d_work, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (words > 0) PTMI_HIP(c, hipMemcpyAsync(out, c->d_work.p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     return words;
 }
@@ -1783,10 +1837,10 @@ int ptmi_reset_stats(ptmi_ctx *c)
     std::lock_guard<std::mutex> lock(c->mu);
     PTMI_HIP(c, hipSetDevice(c->device));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_live, 0, kLiveBytes, c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_iters, 0, kItersBytes, c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_work, 0, kWorkWords * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_stream_counters, 0, kScWords * sizeof(unsigned long long), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(c->d_live.p, 0, kLiveBytes, c->stream));
+    PTMI_HIP(c, hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream));
+    PTMI_HIP(c, hipMemsetAsync(c->d_work.p, 0, kWorkWords * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(c->d_stream_counters.p, 0, kScWords * sizeof(unsigned long long), c->stream));
     c->nominal = 0; c->samples = 0; c->rays_dropped = 0; c->rays_truncated = 0; c->rays_spilled = 0; c->rays_overflowed = 0; c->live_host = 0;
     return PTMI_OK;
 }
@@ -1801,8 +1855,8 @@ static int eval_prims(ptmi_ctx *c, const void *prims, int words, const float *ra
     PTMI_HIP(c, hipSetDevice(c->device));
     const size_t nb = (size_t)n;
     const size_t bytes = nb * (words * 4 + 6 * 4 + 4 + 4 + 6 * 4);
-    if (int rc = ensure_scratch(c, bytes)) return rc;
-    float *d_prims = static_cast<float *>(c->scratch);
+    if (int rc = grow(c, c->scratch, bytes, "scratch")) return rc;
+    float *d_prims = c->scratch.as<float>();
     float *d_rays = d_prims + nb * words;
     int32_t *d_just = reinterpret_cast<int32_t *>(d_rays + nb * 6);
     float *d_t = reinterpret_cast<float *>(d_just + nb);
@@ -1840,8 +1894,8 @@ int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *
     if (n == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
     const size_t nb = (size_t)n;
-    if (int rc = ensure_scratch(c, nb * 12)) return rc;
-    float *dx = static_cast<float *>(c->scratch), *ds = dx + nb, *dc = ds + nb;
+    if (int rc = grow(c, c->scratch, nb * 12, "scratch")) return rc;
+    float *dx = c->scratch.as<float>(), *ds = dx + nb, *dc = ds + nb;
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     PTMI_HIP(c, hipMemcpyAsync(dx, x, nb * 4, hipMemcpyHostToDevice, c->stream));
     PTMI_HIP(c, launch_eval_sincos(dx, n, ds, dc, c->stream));
