@@ -21,6 +21,9 @@ ARITH_EXACT, ARITH_CONTRACTED = 0, 1
 SEED_KEEP_ACCUMULATOR, SEED_FROM_RESULT, SEED_AUTO = 0, 1, 2
 FORM_AUTO, FORM_STREAM, FORM_PIXEL = 0, 1, 2
 PTMI_OK, PTMI_EINVAL, PTMI_ENODEVICE, PTMI_EHIP, PTMI_ENOMEM, PTMI_ESTATE, PTMI_ELIMIT, PTMI_ESTALE = 0, -1, -2, -3, -4, -5, -6, -7
+MAX_PRIMITIVES, MAX_BVH_SPHERES, MAX_BVH_PLANES, BVH_MAX_DEPTH, BVH_LEAF_MAX = 1024, 1 << 22, 64, 24, 4
+# ptmi_bvh_node: the boxes of both children (centre, half extent), the child references, 1 / (2 r_min) per child
+BVH_NODE_DTYPE = np.dtype([("center", "<f4", (2, 3)), ("half", "<f4", (2, 3)), ("ref", "<i4", 2), ("inv_2r", "<f4", 2)])
 
 # every symbol include/ptmi.h declares: name -> (restype, argtypes)
 _f32p, _u32p, _i32p, _i64p, _vp = (C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
@@ -46,6 +49,8 @@ SYMBOLS = {
     "ptmi_destroy": (None, [_vp]),
     "ptmi_last_error": (C.c_char_p, [_vp]),
     "ptmi_set_scene": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_bvh_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "ptmi_local_rows": (C.c_int, [_vp]),
@@ -82,6 +87,7 @@ SYMBOLS = {
     "ptmi_group_member": (_vp, [_vp, C.c_int]),
     "ptmi_group_last_error": (C.c_char_p, [_vp]),
     "ptmi_group_set_scene": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_group_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_group_init_output": (C.c_int, [_vp, C.c_uint64]),
     "ptmi_group_reseed": (C.c_int, [_vp, C.c_uint64]),
@@ -102,6 +108,7 @@ SYMBOLS = {
     "ptmi_stream_tickets": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int]),
     "ptmi_eval_distance_to_sphere": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_distance_to_plane": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_eval_check_hit": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
 }
 
@@ -168,6 +175,18 @@ def stream_tickets(option, first, queue_regions):
     return list(zip(p[:got].tolist(), r[:got].tolist()))
 
 
+def bvh_layout(spheres):
+    """ptmi_bvh_layout: the hierarchy ptmi_set_scene_bvh builds over these spheres (host code, no device) -> (nodes as a
+    BVH_NODE_DTYPE array, node 0 the root; order: the original index of every position of the leaf order)."""
+    s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    nodes = np.zeros(max(1, s.size), BVH_NODE_DTYPE)
+    order = np.zeros(s.size, np.int32)
+    got = load_library().ptmi_bvh_layout(_ptr(s) if s.size else None, s.size, _ptr(nodes), nodes.size, _ptr(order) if s.size else None)
+    if got < 0:
+        raise PtmiError(got, "ptmi_bvh_layout")
+    return nodes[:got].copy(), order
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(_vp)
 
@@ -220,6 +239,13 @@ class Context:
         p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
         self._check(self._lib.ptmi_set_scene(self._h, _ptr(s) if s.size else None, s.size,
                                              _ptr(p) if p.size else None, p.size))
+
+    def set_scene_bvh(self, spheres, planes):
+        """ptmi_set_scene_bvh: the same scene semantics, the spheres through a bounding-volume hierarchy (up to MAX_BVH_SPHERES)."""
+        s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+        p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
+        self._check(self._lib.ptmi_set_scene_bvh(self._h, _ptr(s) if s.size else None, s.size,
+                                                 _ptr(p) if p.size else None, p.size))
 
     def set_partition(self, stripe_rows, n_parts, part):
         self._check(self._lib.ptmi_set_partition(self._h, stripe_rows, n_parts, part))
@@ -427,6 +453,14 @@ class Context:
         self._check(self._lib.ptmi_eval_distance_to_plane(self._h, _ptr(p), _ptr(r), n, _ptr(just), _ptr(t), _ptr(nrm)))
         return just, t, nrm
 
+    def eval_check_hit(self, rays):
+        """ptmi_eval_check_hit: checkHit on the device against the current scene for rays (n x 6) -> (t, idx, just); a miss is t 0, idx -1."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        t, idx, just = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.int32)
+        self._check(self._lib.ptmi_eval_check_hit(self._h, _ptr(r), n, _ptr(t), _ptr(idx), _ptr(just)))
+        return t, idx, just
+
     def eval_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
         s, c = np.empty_like(x), np.empty_like(x)
@@ -484,6 +518,11 @@ class Group:
         s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
         p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
         self._check(self._lib.ptmi_group_set_scene(self._h, _ptr(s) if s.size else None, s.size, _ptr(p) if p.size else None, p.size))
+
+    def set_scene_bvh(self, spheres, planes):
+        s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+        p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
+        self._check(self._lib.ptmi_group_set_scene_bvh(self._h, _ptr(s) if s.size else None, s.size, _ptr(p) if p.size else None, p.size))
 
     def resize(self, width, height):
         self._check(self._lib.ptmi_group_resize(self._h, width, height))

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "ptmi_bvh.h"
 #include "ptmi_kernels.h"
 #include "ptmi_stage.h"
 
@@ -51,6 +52,10 @@ struct ptmi_ctx {
 
     DeviceBlock d_scene;     // float4s: pack_scene
     int n_spheres = 0, n_planes = 0;
+    // a BVH scene (ptmi_set_scene_bvh): d_scene as ever, and the hierarchy -- nodes, the spheres in leaf order, their indices -- in d_bvh
+    bool scene_bvh = false;
+    DeviceBlock d_bvh;
+    BvhView bvh{};
 
     DeviceBlock d_live;      // unsigned long long
     DeviceBlock d_work;      // unsigned int
@@ -147,7 +152,7 @@ struct ptmi_ctx {
     // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
     template <class F> void each_block(F &&f)
     {
-        for (DeviceBlock *b : {&owned_block, &d_scene, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
                                &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
                                &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
             f(*b);
@@ -196,6 +201,7 @@ int effective_seed_rule(const ptmi_ctx *c)
 bool uses_stream_form(const ptmi_ctx *c, int algorithm, int n_parts, int n_spp)
 {
     if (algorithm != PTMI_STREAMS) return false;
+    if (c->scene_bvh) return false;                      // (a BVH scene renders through the per-pixel kernels only)
     if (c->opt_form == PTMI_FORM_STREAM || c->variant == 9) return true;
     if (c->opt_form == PTMI_FORM_PIXEL) return false;
     return c->has_glass && n_parts > 1 && (n_spp < 0 || n_spp >= 256);
@@ -924,7 +930,18 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
         a.spp_chunks = sx ? 1 : c->opt_spp_chunks;
     }
     if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev0, c->stream)); }
-    if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
+    if (c->scene_bvh) {                                    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
+        if (algorithm == PTMI_INLINE) {
+            PTMI_HIP(c, launch_render_inline_bvh(a, c->bvh, c->stream));
+        } else if (c->has_glass) {
+            const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
+            if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
+            a.tree_stack = c->tree_stack.as<float4>();
+            PTMI_HIP(c, launch_render_streams_tree_bvh(a, c->bvh, c->stream));
+        } else {
+            PTMI_HIP(c, launch_render_streams_bvh(a, c->bvh, c->stream));
+        }
+    } else if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
         PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == 9 ? 0 : c->variant, c->stream));
     } else if (algorithm == PTMI_INLINE) {
         PTMI_HIP(c, launch_render_inline(a, c->variant, c->stream));
@@ -960,6 +977,8 @@ int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int
         return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
     if (algorithm == PTMI_STREAMS && c->has_glass && c->opt_seed_rule == PTMI_SEED_FROM_RESULT)
         return fail(c, PTMI_EINVAL, "PTMI_SEED_FROM_RESULT is undefined when rays split (GLASS): several results race for one pixel's seed");
+    if (c->scene_bvh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+        return fail(c, PTMI_EINVAL, "a BVH scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
     return PTMI_OK;
 }
 
@@ -1245,13 +1264,77 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed` dies at return
     if (e != hipSuccess) { release(fresh); PTMI_HIP(c, e); }
     release(c->d_scene);
+    release(c->d_bvh);
     c->d_scene = fresh;
+    c->scene_bvh = false; c->bvh = BvhView{};
     c->n_spheres = n_spheres; c->n_planes = n_planes;
     ++c->scene_version;
     c->has_glass = false;
     for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
     for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
     return PTMI_OK;
+}
+
+int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+#ifdef PTMI_ABLATIONS
+    (void)spheres; (void)n_spheres; (void)planes; (void)n_planes;
+    return fail(c, PTMI_EINVAL, "the ablation library has no BVH kernels: use libptmi for BVH scenes");
+#else
+    if (n_spheres < 0 || n_planes < 0 || (n_spheres > 0 && !spheres) || (n_planes > 0 && !planes))
+        return fail(c, PTMI_EINVAL, "bad scene arguments");
+    if (n_spheres + n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
+    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
+    if (n_planes > PTMI_MAX_BVH_PLANES) return fail(c, PTMI_ELIMIT, "more planes than PTMI_MAX_BVH_PLANES");
+    if (c->variant != 0) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
+    if (c->opt_form == PTMI_FORM_STREAM)
+        return fail(c, PTMI_EINVAL, "a BVH scene has no stream form: set PTMI_OPT_STREAMS_FORM to PTMI_FORM_AUTO or PTMI_FORM_PIXEL first");
+    for (int i = 0; i < n_spheres; ++i)
+        if (spheres[i].brdf_tag < PTMI_MATTE || spheres[i].brdf_tag > PTMI_GLASS)
+            return fail(c, PTMI_EINVAL, "sphere with unknown brdf_tag");
+    for (int j = 0; j < n_planes; ++j)
+        if (planes[j].brdf_tag < PTMI_MATTE || planes[j].brdf_tag > PTMI_GLASS)
+            return fail(c, PTMI_EINVAL, "plane with unknown brdf_tag");
+    BvhBuild bb;
+    std::string why;
+    if (int rc = bvh_build(spheres, n_spheres, bb, &why)) return fail(c, rc, why);
+    PTMI_HIP(c, hipSetDevice(c->device));
+    std::vector<float4> packed;
+    pack_scene(spheres, n_spheres, planes, n_planes, packed);
+    // d_bvh: the nodes (four float4 each), the spheres in leaf order as pack_scene makes them, their original indices
+    const size_t nodes_f4 = bb.nodes.size() * 4, geom_f4 = (size_t)n_spheres;
+    std::vector<float4> hier(nodes_f4 + geom_f4 + ((size_t)n_spheres + 3) / 4);
+    std::memcpy(hier.data(), bb.nodes.data(), bb.nodes.size() * sizeof(ptmi_bvh_node));
+    for (int k = 0; k < n_spheres; ++k) hier[nodes_f4 + (size_t)k] = packed[(size_t)bb.order[(size_t)k]];
+    if (n_spheres > 0) std::memcpy(&hier[nodes_f4 + geom_f4], bb.order.data(), (size_t)n_spheres * sizeof(int32_t));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    // both blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
+    DeviceBlock fresh, fresh_bvh;
+    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
+    hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed` and `hier` die at return
+    if (e != hipSuccess) { release(fresh); release(fresh_bvh); PTMI_HIP(c, e); }
+    release(c->d_scene);
+    release(c->d_bvh);
+    c->d_scene = fresh;
+    c->d_bvh = fresh_bvh;
+    c->scene_bvh = true;
+    const float4 *base = c->d_bvh.as<float4>();
+    c->bvh.nodes = base;
+    c->bvh.geom = base + nodes_f4;
+    c->bvh.index = reinterpret_cast<const int *>(base + nodes_f4 + geom_f4);
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
+    c->n_spheres = n_spheres; c->n_planes = n_planes;
+    ++c->scene_version;
+    c->has_glass = false;
+    for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
+    for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    return PTMI_OK;
+#endif
 }
 
 int ptmi_set_partition(ptmi_ctx *c, int stripe_rows, int n_parts, int part)
@@ -1364,6 +1447,7 @@ int ptmi_set_variant(ptmi_ctx *c, int variant)
     std::lock_guard<std::mutex> lock(c->mu);
     if (variant < 0 || variant > 18) return fail(c, PTMI_EINVAL, "unknown variant");
     if (!variant_available(variant)) return fail(c, PTMI_EINVAL, "this variant is an ablation kernel: build libptmi with -DPTMI_ABLATIONS");
+    if (c->scene_bvh && variant != 0) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
     c->variant = variant;
     return PTMI_OK;
 }
@@ -1424,6 +1508,7 @@ int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
         return PTMI_OK;
     case PTMI_OPT_STREAMS_FORM:
         if (value != PTMI_FORM_AUTO && value != PTMI_FORM_STREAM && value != PTMI_FORM_PIXEL) return fail(c, PTMI_EINVAL, "unknown Streams form");
+        if (c->scene_bvh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a BVH scene has no stream form (PTMI_FORM_STREAM)");
         c->opt_form = (int)value; return PTMI_OK;
     case PTMI_OPT_STREAM_BATCH:
         if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "stream batch must be in [0, 64] samples");
@@ -1884,6 +1969,31 @@ int ptmi_eval_distance_to_plane(ptmi_ctx *c, const ptmi_plane *planes, const flo
                                 int32_t *is_just, float *t, float *hit_normalp)
 {
     return eval_prims(c, planes, 12, rays, n, is_just, t, hit_normalp, false);
+}
+
+int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int32_t *idx_out, int32_t *just_out)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!rays || !t_out || !idx_out || !just_out))) return fail(c, PTMI_EINVAL, "bad point-query arguments");
+    if (!c->d_scene.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (n == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)n;
+    if (int rc = grow(c, c->scratch, nb * (6 * 4 + 3 * 4), "scratch")) return rc;
+    float *d_rays = c->scratch.as<float>();
+    float *d_t = d_rays + nb * 6;
+    int32_t *d_idx = reinterpret_cast<int32_t *>(d_t + nb), *d_just = d_idx + nb;
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(d_rays, rays, nb * 6 * 4, hipMemcpyHostToDevice, c->stream));
+    SceneView scene;
+    scene.packed = c->d_scene.as<float4>(); scene.n_spheres = c->n_spheres; scene.n_planes = c->n_planes;
+    PTMI_HIP(c, launch_eval_check_hit(scene, c->scene_bvh ? &c->bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(t_out, d_t, nb * 4, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(idx_out, d_idx, nb * 4, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(just_out, d_just, nb * 4, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
 }
 
 int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *cos_out)

@@ -106,6 +106,17 @@ __device__ __noinline__ HitSel check_hit_exact(ScenePtr S, int ns, int np, V3 o,
     return best;
 }
 
+// distanceTo @Sphere (Intersection.hs:39-48) up to the square root, for g = (cx, cy, cz, r*r): declares tca, x and cand.  t = tca -
+// sqrt_rn(x) (min t0 t1 == t0), Just iff cand && !(t < 0).  A macro, so that check_hit and check_hit_bvh (ptmi_bvh_device.h) make
+// the SAME operations -- a BVH scene's hits are bit for bit the linear fold's -- and check_hit's code stays what it was.
+#define PTMI_SPHERE_TEST(g, o, d)                                                                                                   \
+    const V3 l = mk(g.x, g.y, g.z) - o;                                                                                             \
+    const float tca = dot(l, d);                                                                                                    \
+    const float d2 = dot(l, l) - (tca * tca);                                                                                       \
+    const float x = g.w - d2;                            /* rad ** 2 - d2 (rad ** 2 squared at upload) */                           \
+    /* Nothing iff tca < 0 || d2 > rad**2 || t < 0;  d2 > r2 <=> r2 - d2 < 0 (exact: gradual underflow) */                         \
+    const bool cand = !(tca < 0.0f) && !(x < 0.0f)
+
 // check_hit is the same fold shaped for the SIMD:
 //   * the cheap part of every test (16 f32 operations for a sphere) runs for all lanes; the square
 //     root / division and the fold update run only when some lane of the wave can still be hit
@@ -130,13 +141,7 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
     bool best_just = false;
 
     auto sphere = [&](const float4 g, int i) {
-        // distanceTo @Sphere (Intersection.hs:39-48)
-        const V3 l = mk(g.x, g.y, g.z) - o;
-        const float tca = dot(l, d);
-        const float d2 = dot(l, l) - (tca * tca);
-        const float x = g.w - d2;                            // rad ** 2 - d2 (rad ** 2 squared at upload)
-        // Nothing iff tca < 0 || d2 > rad**2 || t < 0;  d2 > r2 <=> r2 - d2 < 0 (exact: gradual underflow)
-        const bool cand = !(tca < 0.0f) && !(x < 0.0f);
+        PTMI_SPHERE_TEST(g, o, d);                           // tca, x, cand
         diag::sphere_test(diag, cand);
         if (__any(cand)) {
             const float t = tca - sqrt_rn(x);                // min t0 t1 == t0 (thc >= 0 or NaN)

@@ -28,6 +28,15 @@ struct SceneView {
     __host__ __device__ int total_f4() const { return geom_f4() + 2 * (n_spheres + n_planes); }
 };
 
+// The sphere hierarchy of a BVH scene (ptmi_set_scene_bvh; ptmi_bvh_device.h walks it).  The packed scene above stays as it is (the
+// materials, the planes, hit_record by original index); the spheres are tested through `geom`.
+struct BvhView {
+    const float4 *nodes;      // ptmi_bvh_node, four float4 each: (c0 xyz, c1 x) (c1 yz, h0 xy) (h0 z, h1 xyz) (ref0, ref1, inv_2r0, inv_2r1)
+    const float4 *geom;       // the spheres in leaf order: (cx, cy, cz, r*r), as pack_scene makes them
+    const int *index;         // ... and their original indices
+    float lo[3], hi[3];       // box of the sphere centres
+};
+
 struct Planes {
     float *r, *g, *b;
     uint32_t *sa, *sb, *sc, *sctr;
@@ -205,6 +214,11 @@ hipError_t launch_render_inline(const RenderArgs &a, int variant, hipStream_t st
 bool variant_available(int variant);     // ablation variants exist only in builds with -DPTMI_ABLATIONS
 hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool big_scene, hipStream_t stream);   // ptmi_inline_ablations.hip (-DPTMI_ABLATIONS)
 hipError_t launch_render_streams(const RenderArgs &a, int variant, hipStream_t stream);
+// BVH scenes: the same three per-pixel kernels with the hierarchy's hit search (render_*_bvh_kernel), and checkHit as a point query
+hipError_t launch_render_inline_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
+hipError_t launch_render_streams_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
+hipError_t launch_render_streams_tree_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
+hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
 hipError_t launch_render_streams_tree(const RenderArgs &a, int variant, hipStream_t stream);   // scenes with GLASS: per-pixel tree walk
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only

@@ -1,7 +1,7 @@
 // ptmi_small.hip -- the HBM-streaming kernels around the render kernels: genSeeds / createWith / initialOutput / reseed
 // (src/Util.hs:122-135, 204-205), present (app/Main.hs:351, app/assets/fs.glsl:12), the group read-out's stitch, the cost order of
 // the tiled kernels' dispatch, and the point queries behind the reference's unit-test surface (test/Scene/Intersection/Tests.hs).
-#include "ptmi_device.h"
+#include "ptmi_bvh_device.h"
 
 namespace ptmi {
 
@@ -123,6 +123,23 @@ __global__ void __launch_bounds__(kBlock) eval_sphere_kernel(const float *sph, c
     }
 }
 
+// checkHit (Trace.hs:443-447) on the context's scene for host rays: the render kernels' hit search (check_hit over the packed scene,
+// check_hit_bvh over a BVH scene), one lane per ray.  A miss is reported as t = 0, idx = -1.
+template <bool BVH>
+__global__ void __launch_bounds__(kRenderBlock) eval_check_hit_kernel(const SceneView scene, const BvhView bvh, const float *rays, int n,
+                                                                      float *t_out, int32_t *idx_out, int32_t *just_out)
+{
+    const int i = blockIdx.x * kRenderBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
+    const V3 d = mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
+    const HitSel h = BVH ? check_hit_bvh(bvh, scene.packed, scene.n_spheres, scene.n_planes, o, d)
+                         : check_hit(scene.packed, scene.n_spheres, scene.n_planes, o, d);
+    just_out[i] = h.just ? 1 : 0;
+    t_out[i] = h.just ? h.t : 0.0f;
+    idx_out[i] = h.just ? h.idx : -1;
+}
+
 __global__ void __launch_bounds__(kBlock) eval_plane_kernel(const float *pl, const float *rays, int n,
                                                             int32_t *is_just, float *t_out, float *normalp)
 {
@@ -237,6 +254,14 @@ hipError_t launch_eval_sphere(const float *spheres10, const float *rays, int n,
 {
     if (n <= 0) return hipSuccess;
     return launch(eval_sphere_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, spheres10, rays, n, is_just, t, normalp);
+}
+
+hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const dim3 grid(blocks_for(n, kRenderBlock)), block(kRenderBlock);
+    if (bvh) return launch(eval_check_hit_kernel<true>, grid, block, 0, stream, scene, *bvh, rays, n, t, idx, just);
+    return launch(eval_check_hit_kernel<false>, grid, block, 0, stream, scene, BvhView{}, rays, n, t, idx, just);
 }
 
 hipError_t launch_eval_plane(const float *planes12, const float *rays, int n,

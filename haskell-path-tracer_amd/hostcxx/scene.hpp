@@ -152,16 +152,26 @@ constexpr int maxIterations = 15;                                        // Trac
 }  // namespace Trace
 
 // ---- the device context (what runN's backend state is to the reference) -------------------------
+// How the context holds the scene: Linear (ptmi_set_scene, up to PTMI_MAX_PRIMITIVES primitives) or Bvh (ptmi_set_scene_bvh: the
+// spheres in a bounding-volume hierarchy, up to PTMI_MAX_BVH_SPHERES; the same images, bit for bit).
+enum class SceneKind { Linear, Bvh };
+
 class Device {
 public:
     explicit Device(int device = 0, int screenWidth = 800, int screenHeight = 600,        // Util.hs:186-188
-                    const SceneDescription &scene = World::mainScene())
+                    const SceneDescription &scene = World::mainScene(), SceneKind kind = SceneKind::Linear)
         : width_(screenWidth), height_(screenHeight)
     {
         ptmi_ctx *raw = nullptr;
         const int rc = ptmi_create(&raw, device);
         if (rc != PTMI_OK) throw PtmiError(rc, ptmi_last_error(nullptr));
         ctx_.reset(raw, ptmi_destroy);
+        setScene(scene, kind);
+        check(ptmi_resize(raw, width_, height_));
+    }
+    // replaces the scene (transactional: on an exception the context keeps the scene it had)
+    void setScene(const SceneDescription &scene, SceneKind kind = SceneKind::Linear)
+    {
         std::vector<ptmi_sphere> sp;
         std::vector<ptmi_plane> pl;
         for (const Sphere &s : scene.spheres)
@@ -173,8 +183,8 @@ public:
                                     {p.direction.x, p.direction.y, p.direction.z},
                                     {p.material.color.x, p.material.color.y, p.material.color.z},
                                     p.material.illuminance, p.material.brdf.tag, p.material.brdf.parameter});
-        check(ptmi_set_scene(raw, sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
-        check(ptmi_resize(raw, width_, height_));
+        if (kind == SceneKind::Bvh) check(ptmi_set_scene_bvh(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
+        else check(ptmi_set_scene(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
     }
     ptmi_ctx *get() const { return ctx_.get(); }
     const std::shared_ptr<ptmi_ctx> &shared() const { return ctx_; }

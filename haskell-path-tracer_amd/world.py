@@ -104,3 +104,38 @@ def screen_pixels(width, height):
     """screenPixels (src/Util.hs:209-210): Matrix (V2 Int), V2 x y at index (Z :. y :. x)."""
     ys, xs = np.meshgrid(np.arange(height, dtype=np.int64), np.arange(width, dtype=np.int64), indexing="ij")
     return np.ascontiguousarray(xs), np.ascontiguousarray(ys)
+
+
+def sphere_field(n_spheres, seed=0, glass_fraction=0.0):
+    """A seeded random field of n_spheres small spheres in front of initial_camera(), between main_scene()'s floor and ceiling,
+    with a back wall and a side wall: 4 planes.  The field is a layer about 0.5 spheres per unit volume dense, as wide and
+    deep as it needs to be (10 units for 1 000 spheres, 340 for 10^6); radii 0.1 .. 0.45; matte and glossy, 2 % of them
+    emissive; glass_fraction of them GLASS (build-defined: render Streams only).  For BVH scenes (ptmi_set_scene_bvh) --
+    tests and tools/bvh_bench.py.  -> (spheres, planes)"""
+    rng = np.random.default_rng(seed)
+    n = int(n_spheres)
+    y0, y1 = -2.8, 14.8
+    w = float(np.sqrt(max(n, 1) / (0.5 * (y1 - y0))))
+    s = np.zeros(n, dtype=SPHERE_DTYPE)
+    s["position"][:, 0] = 1.0 + (rng.random(n, dtype=np.float32) - 0.5) * w
+    s["position"][:, 1] = y0 + rng.random(n, dtype=np.float32) * (y1 - y0)
+    s["position"][:, 2] = -6.0 - rng.random(n, dtype=np.float32) * w
+    s["radius"] = 0.1 + 0.35 * rng.random(n, dtype=np.float32)
+    s["color"] = 0.2 + 0.75 * rng.random((n, 3), dtype=np.float32)
+    s["illuminance"] = np.where(rng.random(n) < 0.02, 50.0 + 400.0 * rng.random(n), 0.0).astype(np.float32)
+    glossy = rng.random(n) < 0.3
+    s["brdf_tag"] = np.where(glossy, GLOSSY, MATTE)
+    s["brdf_param"] = np.where(glossy, 0.6 + 0.4 * rng.random(n), 0.5 + 0.5 * rng.random(n)).astype(np.float32)
+    if glass_fraction > 0.0:
+        glass = rng.random(n) < glass_fraction
+        s["brdf_tag"][glass] = GLASS
+        s["brdf_param"][glass] = 1.5
+        s["color"][glass] = (0.95, 0.95, 0.95)
+        s["illuminance"][glass] = 0.0
+    planes = np.array([
+        plane((0.0, -3.0, 0.0), (0.0, 1.0, 0.0), (0.43, 0.95, 0.5), 0.0, MATTE, 1.5),
+        plane((0.0, 15.0, 0.0), (0.0, -1.0, 0.0), (0.26, 0.68, 0.88), 0.0, GLOSSY, 0.9),
+        plane((0.0, 0.0, -6.0 - w - 4.0), (0.0, 0.0, 1.0), (0.9, 0.9, 0.9), 2.0, MATTE, 1.0),
+        plane((1.0 - 0.5 * w - 4.0, 0.0, 0.0), (1.0, 0.0, 0.0), (0.8, 0.5, 0.4), 0.0, GLOSSY, 0.7),
+    ], dtype=PLANE_DTYPE)
+    return s, planes

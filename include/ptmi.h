@@ -39,7 +39,9 @@ extern "C" {
                             * options 14 and 15, PTMI_FORM_PIXEL; ordered passes hand off with release / acquire per region; ptmi_build_id names the
                             * compiled code, not the source text.  0.5.0: ptmi_build_id; ptmi_debug_counters writes 64 words again (as in 0.3) and ptmi_debug_counters_n takes a
                             * capacity; option 13 and ptmi_stream_tickets; the stream form's overflow streams grow instead of dropping children;
-                            * no option is read from the environment any more.  (0.4.0: options 8-12, ptmi_stream_schedule.) */
+                            * no option is read from the environment any more.  (0.4.0: options 8-12, ptmi_stream_schedule.)
+                            * Added without a version bump: the bounding-volume-hierarchy scene (ptmi_set_scene_bvh, ptmi_group_set_scene_bvh,
+                            * ptmi_bvh_layout, ptmi_bvh_node, PTMI_MAX_BVH_*) and ptmi_eval_check_hit. */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -49,7 +51,7 @@ enum {
     PTMI_EHIP      = -3,   /* a HIP runtime call failed; message in ptmi_last_error          */
     PTMI_ENOMEM    = -4,   /* device or host allocation failed                                */
     PTMI_ESTATE    = -5,   /* call order violated (render before set_scene / resize ...)     */
-    PTMI_ELIMIT    = -6,   /* scene larger than PTMI_MAX_PRIMITIVES; an image of more than 2^40 pixels (or beyond the stream form's limits) */
+    PTMI_ELIMIT    = -6,   /* scene larger than PTMI_MAX_PRIMITIVES (PTMI_MAX_BVH_* for ptmi_set_scene_bvh); an image of more than 2^40 pixels (or beyond the stream form's limits) */
     PTMI_ESTALE    = -7    /* a token names no state this context holds (released, consumed, or another context's) */
 };
 
@@ -67,6 +69,10 @@ enum { PTMI_STREAMS = 0, PTMI_INLINE = 1 };
 enum { PTMI_MATTE = 0, PTMI_GLOSSY = 1, PTMI_GLASS = 2 };
 
 #define PTMI_MAX_PRIMITIVES 1024   /* spheres + planes staged in LDS per workgroup */
+#define PTMI_MAX_BVH_SPHERES (1 << 22)   /* ptmi_set_scene_bvh: spheres in the hierarchy */
+#define PTMI_MAX_BVH_PLANES  64          /* ... planes, folded linearly after the spheres */
+#define PTMI_BVH_MAX_DEPTH   24          /* levels of inner nodes (the root is level 0); the device keeps one stack entry per level */
+#define PTMI_BVH_LEAF_MAX    4           /* spheres per leaf */
 
 /* ---- scene types: field order = src/Scene/Objects.hs ------------------------ */
 typedef struct ptmi_sphere {       /* data Sphere   Objects.hs:126-131, Material :90-100 */
@@ -86,6 +92,19 @@ typedef struct ptmi_plane {        /* data Plane    Objects.hs:103-108 */
     int32_t brdf_tag;
     float   brdf_param;
 } ptmi_plane;                      /* 12 words */
+
+/* One inner node of the sphere hierarchy of ptmi_set_scene_bvh (ptmi_bvh_layout returns them; node 0 is the root): the boxes of
+ * BOTH children, as centre and half extent, so that one 64-byte fetch tests two boxes.  ref[c] >= 0: child c is inner node ref[c];
+ * ref[c] < 0: child c is a leaf of ((-1 - ref[c]) & 255) spheres starting at position (-1 - ref[c]) >> 8 of the
+ * leaf order; -1 is an empty child.  inv_2r[c] = 1 / (2 r_min), r_min the smallest |radius| under child c (+inf when it is 0): the traversal's margin for
+ * rounding in the sphere test depends on it (DESIGN.md "BVH scenes").  A child's box holds every sphere under it, each padded
+ * (centre +- (|r| (1 + 2^-8) + 2^-20 max(|centre|, |r|))). */
+typedef struct ptmi_bvh_node {
+    float   center[2][3];
+    float   half[2][3];
+    int32_t ref[2];
+    float   inv_2r[2];
+} ptmi_bvh_node;                   /* 16 words */
 
 typedef struct ptmi_camera {       /* data Camera   Objects.hs:67-74 */
     float   position[3];
@@ -136,6 +155,24 @@ const char *ptmi_last_error(const ptmi_ctx *ctx);
  * over spheres then planes (src/Util.hs:156-158) and ties keep the earlier primitive. */
 int ptmi_set_scene(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres,
                    const ptmi_plane *planes, int n_planes);
+
+/* The same scene semantics (spheres then planes; ties keep the earlier primitive: the render is bit for bit the one ptmi_set_scene
+ * would give) for scenes of up to PTMI_MAX_BVH_SPHERES spheres and PTMI_MAX_BVH_PLANES planes: the spheres go into a bounding-volume
+ * hierarchy built on the host (ptmi_bvh_layout), the planes stay a linear list.  Hits are found by walking the hierarchy, so a
+ * bounce costs about log(n) box tests instead of n sphere tests -- and more than the linear fold for small scenes: opt-in.
+ * Fails with PTMI_ELIMIT beyond the limits (0 spheres and 0 planes: PTMI_EINVAL) and with PTMI_EINVAL when a sphere's position,
+ * radius or radius^2 is not finite (a box cannot bound a NaN).  Transactional: after a failure the previous scene, of either kind,
+ * stays.  ptmi_set_scene afterwards (or before) switches representation.  A BVH scene renders through the per-pixel kernels only:
+ * PTMI_OPT_STREAMS_FORM = PTMI_FORM_STREAM, ptmi_set_variant != 0 and the ablation library refuse it with PTMI_EINVAL
+ * (PTMI_FORM_AUTO picks the per-pixel form). */
+int ptmi_set_scene_bvh(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres,
+                       const ptmi_plane *planes, int n_planes);
+
+/* The hierarchy ptmi_set_scene_bvh builds for these spheres, without a device (pure host code, deterministic): node 0 is the root,
+ * order[k] is the original index of the sphere at position k of the leaf order.  `nodes` needs max(1, n_spheres) entries
+ * (node_capacity), `order` n_spheres.  Returns the number of nodes; PTMI_ELIMIT beyond PTMI_MAX_BVH_SPHERES or when node_capacity
+ * is too small, PTMI_EINVAL for NULL pointers or non-finite sphere data. */
+int ptmi_bvh_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
 
 /* screenWidth / screenHeight (src/Util.hs:186-188) as run-time values.  Allocates the
  * seven device planes the context owns (for the rows of its partition, see below) and
@@ -433,6 +470,7 @@ int         ptmi_group_size(const ptmi_group *group);
 ptmi_ctx   *ptmi_group_member(ptmi_group *group, int i);        /* member i's context (options, statistics, planes) */
 const char *ptmi_group_last_error(const ptmi_group *group);      /* per thread, as ptmi_last_error */
 int ptmi_group_set_scene(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes);
+int ptmi_group_set_scene_bvh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_bvh on every member */
 int ptmi_group_resize(ptmi_group *group, int width, int height);
 int ptmi_group_init_output(ptmi_group *group, uint64_t seed0);
 int ptmi_group_reseed(ptmi_group *group, uint64_t seed0);
@@ -467,6 +505,10 @@ int ptmi_eval_distance_to_sphere(ptmi_ctx *ctx, const ptmi_sphere *spheres, cons
                                  int32_t *is_just, float *t, float *hit_normalp);
 int ptmi_eval_distance_to_plane(ptmi_ctx *ctx, const ptmi_plane *planes, const float *rays, int n,
                                 int32_t *is_just, float *t, float *hit_normalp);
+/* checkHit (src/Scene/Trace.hs:443-447) on the DEVICE against the context's current scene, linear or BVH, for n host rays
+ * (n x 6 floats: origin, direction): just_out[i] = 1 if ray i hits, then t_out[i] = its distance and idx_out[i] = the primitive
+ * (spheres 0 .. n_spheres - 1, then planes); for a miss t_out[i] = 0 and idx_out[i] = -1.  The same selection the render kernels make. */
+int ptmi_eval_check_hit(ptmi_ctx *ctx, const float *rays, int n, float *t_out, int32_t *idx_out, int32_t *just_out);
 /* sin/cos of the device math used by anglesToQuaternion, for pinning against libm. */
 int ptmi_eval_sincos(ptmi_ctx *ctx, const float *x, int n, float *sin_out, float *cos_out);
 
