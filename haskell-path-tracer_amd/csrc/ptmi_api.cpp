@@ -71,7 +71,7 @@ struct ptmi_ctx {
     DeviceBlock d_tail_start;   // unsigned int
     int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
     bool ev_valid = false;
-    int variant = 0;
+    int variant = kVariantAuto;
     Stager stager;                          // pinned ring + worker threads for host-buffer entry points (ptmi_stage.h)
 
     // cost-ordered dispatch of the tiled kernels: what every quad of tiles cost in the last launch with this key, and
@@ -202,7 +202,7 @@ bool uses_stream_form(const ptmi_ctx *c, int algorithm, int n_parts, int n_spp)
 {
     if (algorithm != PTMI_STREAMS) return false;
     if (c->scene_bvh) return false;                      // (a BVH scene renders through the per-pixel kernels only)
-    if (c->opt_form == PTMI_FORM_STREAM || c->variant == 9) return true;
+    if (c->opt_form == PTMI_FORM_STREAM || c->variant == kVariantStreamForm) return true;
     if (c->opt_form == PTMI_FORM_PIXEL) return false;
     return c->has_glass && n_parts > 1 && (n_spp < 0 || n_spp >= 256);
 }
@@ -930,31 +930,21 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
         a.spp_chunks = sx ? 1 : c->opt_spp_chunks;
     }
     if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev0, c->stream)); }
-    if (c->scene_bvh) {                                    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
-        if (algorithm == PTMI_INLINE) {
-            PTMI_HIP(c, launch_render_inline_bvh(a, c->bvh, c->stream));
-        } else if (c->has_glass) {
-            const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
-            if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
-            a.tree_stack = c->tree_stack.as<float4>();
-            PTMI_HIP(c, launch_render_streams_tree_bvh(a, c->bvh, c->stream));
-        } else {
-            PTMI_HIP(c, launch_render_streams_bvh(a, c->bvh, c->stream));
-        }
-    } else if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
-        PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == 9 ? 0 : c->variant, c->stream));
+    const BvhView *bvh = c->scene_bvh ? &c->bvh : nullptr;    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
+    if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
+        PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == kVariantStreamForm ? kVariantAuto : c->variant, c->stream));
     } else if (algorithm == PTMI_INLINE) {
-        PTMI_HIP(c, launch_render_inline(a, c->variant, c->stream));
-    } else if (stream_form) {                              // rays travel through streams in HBM (PTMI_OPT_STREAMS_FORM; variant 9)
+        PTMI_HIP(c, launch_render_inline(a, bvh, c->variant, c->stream));
+    } else if (stream_form) {                              // rays travel through streams in HBM (PTMI_OPT_STREAMS_FORM; kVariantStreamForm)
         if (int rc = render_streams_wavefront(c, a, n_spp, *camera)) return rc;
     } else if (c->has_glass) {                             // rays may split: the per-pixel tree walk
         // the first waiting children of every lane as 64-byte records in global memory (ptmi_streams_tree.hip): 16 KB per tile
         const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
         if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
         a.tree_stack = c->tree_stack.as<float4>();
-        PTMI_HIP(c, launch_render_streams_tree(a, c->variant, c->stream));
+        PTMI_HIP(c, launch_render_streams_tree(a, bvh, c->variant, c->stream));
     } else {
-        PTMI_HIP(c, launch_render_streams(a, c->variant, c->stream));
+        PTMI_HIP(c, launch_render_streams(a, bvh, c->variant, c->stream));
     }
     if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev1, c->stream)); c->ev_valid = true; }
     c->order_state = next_order_state;
@@ -1288,7 +1278,7 @@ int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, c
     if (n_spheres + n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
     if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
     if (n_planes > PTMI_MAX_BVH_PLANES) return fail(c, PTMI_ELIMIT, "more planes than PTMI_MAX_BVH_PLANES");
-    if (c->variant != 0) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
+    if (c->variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
     if (c->opt_form == PTMI_FORM_STREAM)
         return fail(c, PTMI_EINVAL, "a BVH scene has no stream form: set PTMI_OPT_STREAMS_FORM to PTMI_FORM_AUTO or PTMI_FORM_PIXEL first");
     for (int i = 0; i < n_spheres; ++i)
@@ -1445,9 +1435,9 @@ int ptmi_set_variant(ptmi_ctx *c, int variant)
 {
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (variant < 0 || variant > 18) return fail(c, PTMI_EINVAL, "unknown variant");
+    if (variant < 0 || variant >= kVariantCount) return fail(c, PTMI_EINVAL, "unknown variant");
     if (!variant_available(variant)) return fail(c, PTMI_EINVAL, "this variant is an ablation kernel: build libptmi with -DPTMI_ABLATIONS");
-    if (c->scene_bvh && variant != 0) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
+    if (c->scene_bvh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
     c->variant = variant;
     return PTMI_OK;
 }

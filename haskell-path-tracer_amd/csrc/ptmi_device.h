@@ -577,6 +577,37 @@ inline hipError_t choose_sample_chunks(RenderArgs &b, unsigned int per_copy, int
     return hipMemsetAsync(b.chunk_done + b.chunk_capacity, 0, sizeof(unsigned int), stream);      // the ticket counter
 }
 
+inline bool renders_nothing(const RenderArgs &a) { return (long long)a.rows_local * a.width <= 0; }
+inline bool scene_fits_lds(const RenderArgs &a) { return (size_t)a.scene.total_f4() * sizeof(float4) <= kMaxSceneLds; }
+
+// How a per-pixel kernel (Inline, the Streams chain, the tree walk) maps waves to pixels: 8x8 tiles once the image has whole tiles and
+// rows of 64 otherwise (kAuto), or the one an explicit variant asks for.
+enum class Mapping { kAuto, kTiles, kRows };
+
+// The launch of a per-pixel kernel: nothing for a part without pixels; the tiled kernel with the sample chunks choose_sample_chunks picks
+// for `waves_per_simd` and `rounds`, or the row kernel over every pixel.  lds_scene: the packed scene is staged in LDS (dynamic LDS of its
+// size), not read through scalar loads.  extra: the kernels' arguments after the RenderArgs (a BVH scene's BvhView).
+template <typename... P, typename... A>
+inline hipError_t launch_per_pixel(const RenderArgs &a, Mapping mapping, void (*tiled)(RenderArgs, P...), void (*rows)(RenderArgs, P...),
+                                   bool lds_scene, int waves_per_simd, unsigned long long rounds, hipStream_t stream, const A &...extra)
+{
+    if (renders_nothing(a)) return hipSuccess;
+    const size_t lds = lds_scene ? (size_t)a.scene.total_f4() * sizeof(float4) : 0;
+    if (mapping == Mapping::kRows || (mapping == Mapping::kAuto && !tiles_pay(a)))
+        return launch(rows, dim3(blocks_for((long long)a.rows_local * a.width, kRenderBlock)), dim3(kRenderBlock), lds, stream, a, extra...);
+    RenderArgs b = a;
+    const unsigned int per_copy = tile_grid(a, 8);
+    if (hipError_t e = choose_sample_chunks(b, per_copy, waves_per_simd, stream, rounds)) return e;
+    return launch(tiled, dim3(per_copy * (unsigned int)b.spp_chunks), dim3(kRenderBlock), lds, stream, b, extra...);
+}
+
+// Streams' step figure is per launch: every shard of stream_iterations starts at zero (nothing for a part that launches nothing)
+inline hipError_t clear_stream_iterations(const RenderArgs &a, hipStream_t stream)
+{
+    if (renders_nothing(a)) return hipSuccess;
+    return hipMemsetAsync(a.stream_iterations, 0, (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), stream);
+}
+
 }  // namespace
 
 }  // namespace ptmi

@@ -50,82 +50,64 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_inline_bv
 }
 #endif
 
+// the linear scenes' kernel: the scene staged in LDS or read through scalar loads, waves on tiles or rows as `mapping` says
+hipError_t launch_linear(const RenderArgs &a, Mapping mapping, bool lds_scene, hipStream_t stream)
+{
+    if (lds_scene) return launch_per_pixel(a, mapping, render_inline_kernel<true, 8>, render_inline_kernel<true>, true, PTMI_INLINE_WAVES, 16, stream);
+    return launch_per_pixel(a, mapping, render_inline_kernel<false, 8>, render_inline_kernel<false>, false, PTMI_INLINE_WAVES, 16, stream);
+}
+
 }  // namespace
 
-// Which render Inline kernel a variant is (ptmi_set_variant):
-//   0 auto | 4 cached, a wave = 64 consecutive pixels of a row (LDS scene) | 5 the same with the scene through scalar loads
-//   13 = 4 with 8x8 pixel tiles per wave | 17 = 5 with 8x8 tiles -- these are what auto chooses from.
-// Only in builds with -DPTMI_ABLATIONS (ptmi_set_variant refuses them otherwise):
-//   1 / 6 persistent hand-out (LDS / scalar-load scene) | 2 lock step | 3 regenerate | 7 / 8 capped occupancy
-//   10-12 pooled second shade round | 14-16 other tile shapes | 18 round 1's loop
-hipError_t launch_render_inline(const RenderArgs &a, int variant, hipStream_t stream)
+hipError_t launch_render_inline(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream)
 {
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 grid(blocks_for(n_local, kRenderBlock)), block(kRenderBlock);
-    const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
-    const bool big_scene = lds > kMaxSceneLds;               // every route reads such a scene through scalar loads, not LDS
-    const bool degenerate = a.bounce_limit <= 0 || a.n_spp <= 0;   // the cached kernel handles both (iterate 0; no sample at all)
-    if (variant == 0 || degenerate) {
-        // static mapping wins at every size measured; a scene so big that staging it per wave would cost more occupancy than scalar loads cost speed is
-        // read through scalar loads; 8x8 tiles once the image is big enough for whole tiles to dominate
-        const bool tiles = tiles_pay(a);
-        variant = !big_scene ? (tiles ? 13 : 4) : (tiles ? 17 : 5);
+    if (renders_nothing(a)) return hipSuccess;
+#ifndef PTMI_CONTRACTED_BUILD
+    if (bvh) return launch_per_pixel(a, Mapping::kAuto, render_inline_bvh_kernel<8>, render_inline_bvh_kernel<0>, false, PTMI_BVH_WAVES, 16, stream, *bvh);
+#endif
+    // static mapping wins at every size measured; a scene so big that staging it per wave would cost more occupancy than
+    // scalar loads cost speed is read through scalar loads (every route); the cached kernel handles the degenerate counts (iterate 0; no sample at all)
+    const bool lds_scene = scene_fits_lds(a);
+    if (variant == kVariantAuto || a.bounce_limit <= 0 || a.n_spp <= 0) return launch_linear(a, Mapping::kAuto, lds_scene, stream);
+    if (!lds_scene) {                                         // the LDS forms would not fit or would cap occupancy
+        if (variant == kVariantPersistent) variant = kVariantPersistentScalar;
+        else if (variant == kVariantRows || variant == kVariantCapped4 || variant == kVariantCapped3) variant = kVariantRowsScalar;
+        else if (variant >= kVariantTiles && variant <= kVariantTiles32x2) variant = kVariantTilesScalar;
     }
-    if (big_scene) {                                         // the LDS forms would not fit or would cap occupancy
-        if (variant == 1) variant = 6;
-        else if (variant == 4 || variant == 7 || variant == 8) variant = 5;
-        else if (variant >= 13 && variant <= 16) variant = 17;
+    switch (variant) {
+    case kVariantRows:        return launch_linear(a, Mapping::kRows, true, stream);
+    case kVariantRowsScalar:  return launch_linear(a, Mapping::kRows, false, stream);
+    case kVariantTiles:       return launch_linear(a, Mapping::kTiles, true, stream);
+    case kVariantTilesScalar: return launch_linear(a, Mapping::kTiles, false, stream);
+    default: break;
     }
-    if (variant == 17 || variant == 13) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t e = choose_sample_chunks(b, per_copy, PTMI_INLINE_WAVES, stream)) return e;
-        const dim3 cgrid(per_copy * (unsigned int)b.spp_chunks);
-        return variant == 17 ? launch(render_inline_kernel<false, 8>, cgrid, block, 0, stream, b)
-                             : launch(render_inline_kernel<true, 8>, cgrid, block, lds, stream, b);
-    }
-    if (variant == 5) return launch(render_inline_kernel<false>, grid, block, 0, stream, a);
-    if (variant == 4) return launch(render_inline_kernel<true>, grid, block, lds, stream, a);
 #if defined(PTMI_ABLATIONS) && !defined(PTMI_CONTRACTED_BUILD)
-    if (variant >= 14 && variant <= 16) {                     // other pixel tiles per wave: 16x4 / 4x16 / 32x2 (8x8 is handled above)
-        const int tw = variant == 14 ? 16 : variant == 15 ? 4 : 32;
+    const dim3 grid(blocks_for((long long)a.rows_local * a.width, kRenderBlock)), block(kRenderBlock);
+    const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
+    if (variant >= kVariantTiles16x4 && variant <= kVariantTiles32x2) {       // other pixel tiles per wave: 16x4 / 4x16 / 32x2 (8x8 is handled above)
+        const int tw = variant == kVariantTiles16x4 ? 16 : variant == kVariantTiles4x16 ? 4 : 32;
         const dim3 tgrid(tile_grid(a, tw));
         if (tw == 16) return launch(render_inline_kernel<true, 16>, tgrid, block, lds, stream, a);
         if (tw == 4)  return launch(render_inline_kernel<true, 4>, tgrid, block, lds, stream, a);
         return launch(render_inline_kernel<true, 32>, tgrid, block, lds, stream, a);
     }
-    if (variant == 7 || variant == 8) {                       // capped occupancy through dynamic LDS: 4 / 3 waves per SIMD
-        return launch(render_inline_kernel<true>, grid, block, (variant == 7 ? 33 : 41) * 1024, stream, a);
-    }
-    return launch_render_inline_ablation(a, variant, big_scene, stream);      // ptmi_inline_ablations.hip
+    if (variant == kVariantCapped4 || variant == kVariantCapped3)             // capped occupancy through dynamic LDS: 4 / 3 waves per SIMD
+        return launch(render_inline_kernel<true>, grid, block, (variant == kVariantCapped4 ? 33 : 41) * 1024, stream, a);
+    return launch_render_inline_ablation(a, variant, !lds_scene, stream);      // ptmi_inline_ablations.hip
 #else
     return hipErrorInvalidValue;                             // ptmi_set_variant admits only what the build holds
 #endif
 }
 
 #ifndef PTMI_CONTRACTED_BUILD
-// render Inline on a BVH scene: the automatic choice of the linear scenes' launcher (8x8 tiles with sample chunks once the image has whole tiles,
-// rows of 64 otherwise); the degenerate counts go through the same kernel.  No variants: ptmi_set_variant refuses them.
-hipError_t launch_render_inline_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream)
-{
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 block(kRenderBlock);
-    if (tiles_pay(a)) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t ce = choose_sample_chunks(b, per_copy, PTMI_BVH_WAVES, stream)) return ce;
-        return launch(render_inline_bvh_kernel<8>, dim3(per_copy * (unsigned int)b.spp_chunks), block, 0, stream, b, bvh);
-    }
-    return launch(render_inline_bvh_kernel<0>, dim3(blocks_for(n_local, kRenderBlock)), block, 0, stream, a, bvh);
-}
-
 bool variant_available(int variant)
 {
-    if (variant == 0 || variant == 4 || variant == 5 || variant == 9 || variant == 13 || variant == 17) return true;
+    switch (variant) {
+    case kVariantAuto: case kVariantRows: case kVariantRowsScalar: case kVariantStreamForm: case kVariantTiles: case kVariantTilesScalar: return true;
+    default: break;
+    }
 #ifdef PTMI_ABLATIONS
-    return variant >= 0 && variant <= 18;
+    return variant >= 0 && variant < kVariantCount;
 #else
     return false;
 #endif
@@ -143,6 +125,6 @@ bool variant_available(int variant)
 // entry, because the two objects' RenderArgs are distinct types of identical layout.
 extern "C" int ptmi_contracted_launch_inline(const void *args, int variant, void *stream)
 {
-    return (int)ptmi::launch_render_inline(*static_cast<const ptmi::RenderArgs *>(args), variant, static_cast<hipStream_t>(stream));
+    return (int)ptmi::launch_render_inline(*static_cast<const ptmi::RenderArgs *>(args), nullptr, variant, static_cast<hipStream_t>(stream));
 }
 #endif

@@ -558,7 +558,7 @@ hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool 
     const long long n_local = (long long)a.rows_local * a.width;
     const dim3 grid(blocks_for(n_local, kRenderBlock)), block(kRenderBlock);
     const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
-    if (variant == 1 || variant == 6) {
+    if (variant == kVariantPersistent || variant == kVariantPersistentScalar) {
         // persistent grid; more workgroups than fit would only start late and find the queue empty: cap at 8 per CU
         int dev = 0, cus = 0;
         hipError_t e = hipGetDevice(&dev);
@@ -568,14 +568,14 @@ hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool 
         const unsigned int blocks = grid.x < (unsigned int)max_blocks ? grid.x : (unsigned int)max_blocks;
         e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), stream);
         if (e != hipSuccess) return e;
-        if (variant == 1) return launch(render_inline_persistent_kernel<true>, dim3(blocks), block, lds, stream, a);
-        else              return launch(render_inline_persistent_kernel<false>, dim3(blocks), block, 0, stream, a);
+        if (variant == kVariantPersistent) return launch(render_inline_persistent_kernel<true>, dim3(blocks), block, lds, stream, a);
+        else                               return launch(render_inline_persistent_kernel<false>, dim3(blocks), block, 0, stream, a);
     }
-    if (variant == 18) {                                      // round 1's loop (no frozen-shade shortcut), 8x8 tiles, LDS scene
+    if (variant == kVariantRound1) {                          // round 1's loop (no frozen-shade shortcut), 8x8 tiles, LDS scene
         return launch(render_inline_modes_kernel<true, kCachedR1, 8>, dim3(tile_grid(a, 8)), block, lds, stream, a);
     }
-    if (variant >= 10 && variant <= 12) {                    // pooled second shade round, W = 2 / 4 / 8 waves per workgroup
-        const int w = variant == 10 ? 2 : variant == 11 ? 4 : 8;
+    if (variant >= kVariantPooled2 && variant <= kVariantPooled8) {      // pooled second shade round, W = 2 / 4 / 8 waves per workgroup
+        const int w = variant == kVariantPooled2 ? 2 : variant == kVariantPooled4 ? 4 : 8;
         const dim3 pgrid(blocks_for(n_local, 64 * w)), pblock(64 * w);
         if (big_scene) {                                       // a scene too big to stage per workgroup: scalar loads
             if (w == 2)      return launch(render_inline_pooled_kernel<false, 2>, pgrid, pblock, 0, stream, a);
@@ -588,10 +588,10 @@ hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool 
         }
     }
     switch (variant) {
-    case 2:  if (big_scene) return launch(render_inline_modes_kernel<false, kLockstep>, grid, block, 0, stream, a);
-             else           return launch(render_inline_modes_kernel<true, kLockstep>, grid, block, lds, stream, a);
-    case 3:  if (big_scene) return launch(render_inline_modes_kernel<false, kRegenerate>, grid, block, 0, stream, a);
-             else           return launch(render_inline_modes_kernel<true, kRegenerate>, grid, block, lds, stream, a);
+    case kVariantLockstep:   if (big_scene) return launch(render_inline_modes_kernel<false, kLockstep>, grid, block, 0, stream, a);
+                             else           return launch(render_inline_modes_kernel<true, kLockstep>, grid, block, lds, stream, a);
+    case kVariantRegenerate: if (big_scene) return launch(render_inline_modes_kernel<false, kRegenerate>, grid, block, 0, stream, a);
+                             else           return launch(render_inline_modes_kernel<true, kRegenerate>, grid, block, lds, stream, a);
     default: break;
     }
     return hipErrorInvalidValue;

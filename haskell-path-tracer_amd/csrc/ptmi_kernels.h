@@ -210,16 +210,39 @@ hipError_t launch_streams_advance_missed(const RenderArgs &a, HitList hits, int 
 hipError_t launch_render_streams_tail(const RenderArgs &a, const unsigned int *first_position, hipStream_t stream);
 unsigned int streams_first_block();   // output slots every wave of a level owns from the start
 
-hipError_t launch_render_inline(const RenderArgs &a, int variant, hipStream_t stream);
-bool variant_available(int variant);     // ablation variants exist only in builds with -DPTMI_ABLATIONS
+// The kernel variants (ptmi_set_variant takes them as an int).  Inline's kernel for each; the ablations exist only in builds with
+// -DPTMI_ABLATIONS (ptmi_set_variant refuses them otherwise).  A scene too big for LDS takes the scalar-load form of an
+// LDS variant (1 -> 6, 4 / 7 / 8 -> 5, 13-16 -> 17).  Streams and the tree walk read 4 / 5 as rows of 64 and 5 / 17 (Streams: 6 too) as
+// scalar loads; 9 is the stream form of Streams (the contracted object renders Inline's automatic choice for it).
+enum Variant : int {
+    kVariantAuto = 0,               // rows or 8x8 tiles, LDS or scalar loads, as the image and the scene make pay
+    kVariantPersistent = 1,         // ablation: persistent hand-out, LDS scene
+    kVariantLockstep = 2,           // ablation: lock step
+    kVariantRegenerate = 3,         // ablation: regenerate only
+    kVariantRows = 4,               // cached, a wave = 64 consecutive pixels of a row, LDS scene
+    kVariantRowsScalar = 5,         // 4 with the scene through scalar loads
+    kVariantPersistentScalar = 6,   // ablation: 1 with the scene through scalar loads
+    kVariantCapped4 = 7,            // ablation: 4 capped at 4 waves per SIMD through dynamic LDS
+    kVariantCapped3 = 8,            // ablation: ... at 3 waves
+    kVariantStreamForm = 9,         // Streams in its stream form
+    kVariantPooled2 = 10,           // ablation: pooled second shade round, 2 / 4 / 8 waves per workgroup
+    kVariantPooled4 = 11,
+    kVariantPooled8 = 12,
+    kVariantTiles = 13,             // 4 with 8x8 pixel tiles per wave
+    kVariantTiles16x4 = 14,         // ablation: other pixel tiles per wave
+    kVariantTiles4x16 = 15,
+    kVariantTiles32x2 = 16,
+    kVariantTilesScalar = 17,       // 5 with 8x8 tiles
+    kVariantRound1 = 18,            // ablation: round 1's loop (no frozen-shade shortcut), 8x8 tiles, LDS scene
+    kVariantCount
+};
+bool variant_available(int variant);
+// The per-pixel kernels of each family; bvh: a BVH scene (ptmi_set_scene_bvh, variant 0 only), null for a linear one
+hipError_t launch_render_inline(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream);
 hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool big_scene, hipStream_t stream);   // ptmi_inline_ablations.hip (-DPTMI_ABLATIONS)
-hipError_t launch_render_streams(const RenderArgs &a, int variant, hipStream_t stream);
-// BVH scenes: the same three per-pixel kernels with the hierarchy's hit search (render_*_bvh_kernel), and checkHit as a point query
-hipError_t launch_render_inline_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
-hipError_t launch_render_streams_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
-hipError_t launch_render_streams_tree_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream);
+hipError_t launch_render_streams(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream);
+hipError_t launch_render_streams_tree(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream);   // scenes with GLASS: per-pixel tree walk
 hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
-hipError_t launch_render_streams_tree(const RenderArgs &a, int variant, hipStream_t stream);   // scenes with GLASS: per-pixel tree walk
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

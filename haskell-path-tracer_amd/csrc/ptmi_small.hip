@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(1024) quad_order_kernel(const unsigned int *co
 // the default (variant 0 = auto) takes the cost order; the explicit variants, 13 and 17 included, keep the image order
 bool uses_quad_order(const RenderArgs &a, int algorithm_inline, int variant)
 {
-    if (variant != 0 || !tiles_pay(a) || a.screen_x) return false;
+    if (variant != kVariantAuto || !tiles_pay(a) || a.screen_x) return false;
     return algorithm_inline ? (a.bounce_limit > 0 && a.n_spp > 0) : true;
 }
 

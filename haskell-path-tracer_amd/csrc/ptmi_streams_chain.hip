@@ -47,47 +47,22 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_streams_b
 #undef PTMI_HIT
 }
 
-}  // namespace
-
-hipError_t launch_render_streams(const RenderArgs &a, int variant, hipStream_t stream)
+// the linear scenes' kernel: the scene staged in LDS or read through scalar loads, waves on tiles or rows as `mapping` says
+hipError_t launch_linear(const RenderArgs &a, Mapping mapping, bool lds_scene, hipStream_t stream)
 {
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 grid(blocks_for(n_local, kRenderBlock)), block(kRenderBlock);
-    const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
-    hipError_t e = hipMemsetAsync(a.stream_iterations, 0, (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), stream);   // every shard: the figure is per launch
-    if (e != hipSuccess) return e;
-    const bool scalar_scene = variant == 5 || variant == 6 || variant == 17 || lds > kMaxSceneLds;
-    const bool tiles = variant == 4 || variant == 5 ? false : tiles_pay(a);      // 4 / 5 keep the row mapping (ablation)
-    if (tiles) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t ce = choose_sample_chunks(b, per_copy, PTMI_STREAMS_WAVES, stream)) return ce;
-        const dim3 tgrid(per_copy * (unsigned int)b.spp_chunks);
-        if (scalar_scene) return launch(render_streams_kernel<false, 8>, tgrid, block, 0, stream, b);
-        else              return launch(render_streams_kernel<true, 8>, tgrid, block, lds, stream, b);
-    } else {
-        if (scalar_scene) return launch(render_streams_kernel<false>, grid, block, 0, stream, a);
-        else              return launch(render_streams_kernel<true>, grid, block, lds, stream, a);
-    }
+    if (lds_scene) return launch_per_pixel(a, mapping, render_streams_kernel<true, 8>, render_streams_kernel<true>, true, PTMI_STREAMS_WAVES, 16, stream);
+    return launch_per_pixel(a, mapping, render_streams_kernel<false, 8>, render_streams_kernel<false>, false, PTMI_STREAMS_WAVES, 16, stream);
 }
 
-// render Streams on a BVH scene: the automatic choice of the linear scenes' launcher (8x8 tiles with sample chunks once the image has whole tiles,
-// rows of 64 otherwise); the degenerate counts go through the same kernel.  No variants: ptmi_set_variant refuses them.
-hipError_t launch_render_streams_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream)
+}  // namespace
+
+hipError_t launch_render_streams(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream)
 {
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 block(kRenderBlock);
-    hipError_t e = hipMemsetAsync(a.stream_iterations, 0, (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), stream);
-    if (e != hipSuccess) return e;
-    if (tiles_pay(a)) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t ce = choose_sample_chunks(b, per_copy, PTMI_BVH_WAVES, stream)) return ce;
-        return launch(render_streams_bvh_kernel<8>, dim3(per_copy * (unsigned int)b.spp_chunks), block, 0, stream, b, bvh);
-    }
-    return launch(render_streams_bvh_kernel<0>, dim3(blocks_for(n_local, kRenderBlock)), block, 0, stream, a, bvh);
+    if (hipError_t e = clear_stream_iterations(a, stream)) return e;
+    if (bvh) return launch_per_pixel(a, Mapping::kAuto, render_streams_bvh_kernel<8>, render_streams_bvh_kernel<0>, false, PTMI_BVH_WAVES, 16, stream, *bvh);
+    const bool rows = variant == kVariantRows || variant == kVariantRowsScalar;          // 4 / 5 keep the row mapping (ablation)
+    const bool scalar = variant == kVariantRowsScalar || variant == kVariantPersistentScalar || variant == kVariantTilesScalar;
+    return launch_linear(a, rows ? Mapping::kRows : Mapping::kAuto, !scalar && scene_fits_lds(a), stream);
 }
 
 // The per-pixel chain kernel as the TAIL of a stream-form launch: a grid over every dispatch position whose workgroups start at
@@ -97,10 +72,7 @@ hipError_t launch_render_streams_tail(const RenderArgs &a, const unsigned int *f
     if (!tiles_pay(a) || !first_position) return hipSuccess;
     RenderArgs b = a;
     b.spp_chunks = 1; b.first_position = first_position;
-    const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
-    const dim3 grid(tile_grid(a, 8)), block(kRenderBlock);
-    if (lds > kMaxSceneLds) return launch(render_streams_kernel<false, 8>, grid, block, 0, stream, b);
-    else                    return launch(render_streams_kernel<true, 8>, grid, block, lds, stream, b);
+    return launch_linear(b, Mapping::kTiles, scene_fits_lds(a), stream);
 }
 
 }  // namespace ptmi

@@ -73,45 +73,16 @@ unsigned int tree_workgroups(int width, int rows_local)
     return (unsigned int)(((long long)width * rows_local + kRenderBlock - 1) / kRenderBlock);
 }
 
-hipError_t launch_render_streams_tree(const RenderArgs &a, int variant, hipStream_t stream)
+hipError_t launch_render_streams_tree(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream)
 {
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 grid(blocks_for(n_local, kRenderBlock)), block(kRenderBlock);
-    const size_t lds = (size_t)a.scene.total_f4() * sizeof(float4);
-    hipError_t e = hipMemsetAsync(a.stream_iterations, 0, (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), stream);   // every shard: the figure is per launch
-    if (e != hipSuccess) return e;
-    const bool scalar_scene = variant == 5 || variant == 17 || lds > kMaxSceneLds;
-    const bool tiles = variant == 4 || variant == 5 ? false : tiles_pay(a);
-    if (tiles) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t ce = choose_sample_chunks(b, per_copy, PTMI_TREE_WAVES, stream, 10)) return ce;
-        const dim3 tgrid(per_copy * (unsigned int)b.spp_chunks);
-        if (scalar_scene) return launch(render_streams_tree_kernel<false, 8>, tgrid, block, 0, stream, b);
-        else              return launch(render_streams_tree_kernel<true, 8>, tgrid, block, lds, stream, b);
-    } else {
-        if (scalar_scene) return launch(render_streams_tree_kernel<false>, grid, block, 0, stream, a);
-        else              return launch(render_streams_tree_kernel<true>, grid, block, lds, stream, a);
-    }
-}
-
-// The tree walk on a BVH scene: the automatic choice of the linear scenes' launcher (8x8 tiles with sample chunks once the image has whole tiles,
-// rows of 64 otherwise); the degenerate counts go through the same kernel.  No variants: ptmi_set_variant refuses them.
-hipError_t launch_render_streams_tree_bvh(const RenderArgs &a, const BvhView &bvh, hipStream_t stream)
-{
-    const long long n_local = (long long)a.rows_local * a.width;
-    if (n_local <= 0) return hipSuccess;
-    const dim3 block(kRenderBlock);
-    hipError_t e = hipMemsetAsync(a.stream_iterations, 0, (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), stream);
-    if (e != hipSuccess) return e;
-    if (tiles_pay(a)) {
-        RenderArgs b = a;
-        const unsigned int per_copy = tile_grid(a, 8);
-        if (hipError_t ce = choose_sample_chunks(b, per_copy, PTMI_BVH_WAVES, stream, 10)) return ce;
-        return launch(render_streams_tree_bvh_kernel<8>, dim3(per_copy * (unsigned int)b.spp_chunks), block, 0, stream, b, bvh);
-    }
-    return launch(render_streams_tree_bvh_kernel<0>, dim3(blocks_for(n_local, kRenderBlock)), block, 0, stream, a, bvh);
+    if (hipError_t e = clear_stream_iterations(a, stream)) return e;
+    if (bvh)
+        return launch_per_pixel(a, Mapping::kAuto, render_streams_tree_bvh_kernel<8>, render_streams_tree_bvh_kernel<0>, false, PTMI_BVH_WAVES, 10, stream, *bvh);
+    // 4 / 5 keep the row mapping (ablation); 5 and 17, not 6, read the scene through scalar loads; 10 rounds of waves (choose_sample_chunks)
+    const Mapping mapping = variant == kVariantRows || variant == kVariantRowsScalar ? Mapping::kRows : Mapping::kAuto;
+    if (variant != kVariantRowsScalar && variant != kVariantTilesScalar && scene_fits_lds(a))
+        return launch_per_pixel(a, mapping, render_streams_tree_kernel<true, 8>, render_streams_tree_kernel<true>, true, PTMI_TREE_WAVES, 10, stream);
+    return launch_per_pixel(a, mapping, render_streams_tree_kernel<false, 8>, render_streams_tree_kernel<false>, false, PTMI_TREE_WAVES, 10, stream);
 }
 
 }  // namespace ptmi

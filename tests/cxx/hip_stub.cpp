@@ -32,7 +32,7 @@
 #include <string>
 #include <vector>
 
-extern "C" void __sanitizer_print_stack_trace(void);
+extern "C" void __sanitizer_print_stack_trace(void) __attribute__((weak));     // (absent from a stand-in built without a sanitizer)
 
 namespace {
 
@@ -62,6 +62,7 @@ struct State {
     std::map<void *, size_t> host_blocks;       // live pinned host blocks
     std::map<const void *, std::string> kernels;        // host stub address -> device name
     std::map<std::string, long> launches;
+    std::string log;                            // what was enqueued, in order, one line each (hipstub_log)
     struct Poke { std::string kernel; long nth; size_t offset; unsigned int value; bool armed; };
     std::vector<Poke> pokes;
     Stream null_stream{kStreamMagic, {}};
@@ -74,6 +75,7 @@ State &S() { static State *state = new State; return *state; }
 #define g_host_blocks (S().host_blocks)
 #define g_kernels (S().kernels)
 #define g_launches (S().launches)
+#define g_log (S().log)
 long g_mallocs = 0;
 long g_streams = 0, g_events = 0;
 long g_calls[6] = {0}, g_fail_at[6] = {0}, g_fail_more[6] = {0};
@@ -94,12 +96,20 @@ bool fails(int kind)
     std::lock_guard<std::mutex> lock(g_mu);
     ++g_calls[kind];
     if (g_fail_at[kind] > 0 && --g_fail_at[kind] == 0) {
-        if (std::getenv("HIPSTUB_TRACE")) { std::fprintf(stderr, "HIPSTUB: injected failure of kind %d here:\n", kind); __sanitizer_print_stack_trace(); }
+        if (std::getenv("HIPSTUB_TRACE")) { std::fprintf(stderr, "HIPSTUB: injected failure of kind %d here:\n", kind); if (__sanitizer_print_stack_trace) __sanitizer_print_stack_trace(); }
         return true;
     }
     if (g_fail_at[kind] == 0 && g_fail_more[kind] > 0) { --g_fail_more[kind]; return true; }      // ... and the calls after it
     return false;
 }
+
+// (bounded: the failure walks enqueue millions of operations and never read the log; past the bound one last line says so)
+void log_line_locked(const std::string &line)
+{
+    constexpr size_t kLogBytes = 1u << 22;
+    if (g_log.size() < kLogBytes) g_log += g_log.size() + line.size() < kLogBytes ? line + "\n" : std::string("truncated\n");
+}
+void log_line(const std::string &line) { std::lock_guard<std::mutex> lock(g_mu); log_line_locked(line); }
 
 hipError_t set(hipError_t e) { if (e != hipSuccess) { g_last = e; g_last_seq = ++g_seq; } return e; }
 
@@ -192,6 +202,16 @@ void hipstub_poke(const char *kernel_part, long nth, unsigned long long offset, 
     std::lock_guard<std::mutex> lock(g_mu);
     S().pokes.push_back(State::Poke{kernel_part ? kernel_part : "", nth, (size_t)offset, value, false});
 }
+// The ordered log of what was enqueued since the last hipstub_clear_log: one line per kernel launch (mangled name, grid, block, dynamic LDS bytes)
+// and per memset (value, bytes) or 32-bit memset (value, words).  The returned text stays valid until the next call of either.
+const char *hipstub_log(void)
+{
+    static std::string copy;
+    std::lock_guard<std::mutex> lock(g_mu);
+    copy = g_log;
+    return copy.c_str();
+}
+void hipstub_clear_log(void) { std::lock_guard<std::mutex> lock(g_mu); g_log.clear(); }
 void hipstub_clear_pokes(void) { std::lock_guard<std::mutex> lock(g_mu); S().pokes.clear(); }
 void hipstub_set_deferred(int on) { flush_all(); g_deferred = on != 0; }
 long hipstub_queued(void)                         // operations waiting for a synchronisation (deferred mode)
@@ -231,7 +251,7 @@ hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *shmem, hip
     return hipSuccess;
 }
 
-hipError_t hipLaunchKernel(const void *function, dim3 grid, dim3 block, void **args, size_t, hipStream_t stream)
+hipError_t hipLaunchKernel(const void *function, dim3 grid, dim3 block, void **args, size_t lds_bytes, hipStream_t stream)
 {
     if (!stream_ok(stream)) return set(hipErrorInvalidHandle);
     if (fails(2)) return set(hipErrorLaunchFailure);
@@ -243,6 +263,8 @@ hipError_t hipLaunchKernel(const void *function, dim3 grid, dim3 block, void **a
     auto it = g_kernels.find(function);
     const std::string name = it == g_kernels.end() ? std::string("<unregistered>") : it->second;
     ++g_launches[name];
+    log_line_locked("launch " + name + " grid " + std::to_string(grid.x) + "," + std::to_string(grid.y) + "," + std::to_string(grid.z) + " block " +
+                    std::to_string(block.x) + "," + std::to_string(block.y) + "," + std::to_string(block.z) + " lds " + std::to_string(lds_bytes));
     for (State::Poke &p : S().pokes)
         if (!p.armed && name.find(p.kernel) != std::string::npos && --p.nth == 0) p.armed = true;
     g_launch_seq = ++g_seq;
@@ -273,7 +295,7 @@ hipError_t hipGetLastError(void)
     const hipError_t e = g_last;
     if (e != hipSuccess && g_last_seq < g_launch_seq) {
         ++g_stale;
-        if (std::getenv("HIPSTUB_TRACE")) { std::fprintf(stderr, "HIPSTUB: an older call's error is handed out after a launch, here:\n"); __sanitizer_print_stack_trace(); }
+        if (std::getenv("HIPSTUB_TRACE")) { std::fprintf(stderr, "HIPSTUB: an older call's error is handed out after a launch, here:\n"); if (__sanitizer_print_stack_trace) __sanitizer_print_stack_trace(); }
     }
     g_last = hipSuccess;
     return e;
@@ -300,7 +322,7 @@ hipError_t hipMalloc(void **p, size_t bytes)
     g_blocks[block] = bytes;
     g_block_seq[block] = ++g_mallocs;
     if (const char *t = std::getenv("HIPSTUB_TRACE_MALLOC"))
-        if (std::atol(t) == g_mallocs) { std::fprintf(stderr, "HIPSTUB: hipMalloc number %ld (%zu bytes) here:\n", g_mallocs, bytes); __sanitizer_print_stack_trace(); }
+        if (std::atol(t) == g_mallocs) { std::fprintf(stderr, "HIPSTUB: hipMalloc number %ld (%zu bytes) here:\n", g_mallocs, bytes); if (__sanitizer_print_stack_trace) __sanitizer_print_stack_trace(); }
     *p = block;
     return hipSuccess;
 }
@@ -384,6 +406,7 @@ hipError_t hipMemsetAsync(void *dst, int value, size_t bytes, hipStream_t stream
 {
     if (!stream_ok(stream)) return set(hipErrorInvalidHandle);
     if (bytes && !dst) return set(hipErrorInvalidValue);
+    log_line("memset " + std::to_string(value) + " bytes " + std::to_string(bytes));
     if (!g_deferred) { std::memset(dst, value, bytes); return hipSuccess; }
     std::lock_guard<std::recursive_mutex> lock(g_queue_mu);
     stream_of(stream)->queue.push_back(Op{Op::Fill, dst, nullptr, bytes, value, nullptr, {}});
@@ -393,6 +416,7 @@ hipError_t hipMemsetD32Async(hipDeviceptr_t dst, int value, size_t count, hipStr
 {
     if (!stream_ok(stream)) return set(hipErrorInvalidHandle);
     if (count && !dst) return set(hipErrorInvalidValue);
+    log_line("memset32 " + std::to_string(value) + " words " + std::to_string(count));
     if (!g_deferred) {
         int *p = static_cast<int *>(dst);
         for (size_t i = 0; i < count; ++i) p[i] = value;
