@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _build
-from .world import CAMERA_DTYPE, PLANE_DTYPE, SPHERE_DTYPE, INLINE, STREAMS
+from .world import CAMERA_DTYPE, PLANE_DTYPE, SPHERE_DTYPE, TRIANGLE_DTYPE, INLINE, STREAMS, triangle  # noqa: F401
 
 OPT_STREAMS_SEED_RULE, OPT_STREAM_STEP_CAP, OPT_STREAM_CAPACITY, OPT_STREAMS_FORM, OPT_STREAM_BATCH, OPT_SPP_CHUNKS, OPT_ARITHMETIC = 1, 2, 3, 4, 5, 6, 7
 OPT_STREAM_TAIL, OPT_ORDERED_PASSES, OPT_GLASS_BATCH, OPT_STREAM_GRADED, OPT_SNAPSHOT_BUDGET_MB, OPT_STREAM_PASS_GROUPS, OPT_CHAIN_SLOTS, OPT_PASS_HANDOFF = 8, 9, 10, 11, 12, 13, 14, 15
@@ -22,6 +22,7 @@ SEED_KEEP_ACCUMULATOR, SEED_FROM_RESULT, SEED_AUTO = 0, 1, 2
 FORM_AUTO, FORM_STREAM, FORM_PIXEL = 0, 1, 2
 PTMI_OK, PTMI_EINVAL, PTMI_ENODEVICE, PTMI_EHIP, PTMI_ENOMEM, PTMI_ESTATE, PTMI_ELIMIT, PTMI_ESTALE = 0, -1, -2, -3, -4, -5, -6, -7
 MAX_PRIMITIVES, MAX_BVH_SPHERES, MAX_BVH_PLANES, BVH_MAX_DEPTH, BVH_LEAF_MAX = 1024, 1 << 22, 64, 24, 4
+MAX_MESH_TRIANGLES = 1 << 22
 # ptmi_bvh_node: the boxes of both children (centre, half extent), the child references, 1 / (2 r_min) per child
 BVH_NODE_DTYPE = np.dtype([("center", "<f4", (2, 3)), ("half", "<f4", (2, 3)), ("ref", "<i4", 2), ("inv_2r", "<f4", 2)])
 
@@ -51,6 +52,8 @@ SYMBOLS = {
     "ptmi_set_scene": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_bvh_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_mesh_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "ptmi_local_rows": (C.c_int, [_vp]),
@@ -88,6 +91,7 @@ SYMBOLS = {
     "ptmi_group_last_error": (C.c_char_p, [_vp]),
     "ptmi_group_set_scene": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_group_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_group_init_output": (C.c_int, [_vp, C.c_uint64]),
     "ptmi_group_reseed": (C.c_int, [_vp, C.c_uint64]),
@@ -187,6 +191,27 @@ def bvh_layout(spheres):
     return nodes[:got].copy(), order
 
 
+def mesh_layout(triangles):
+    """ptmi_mesh_layout: the triangle hierarchy ptmi_set_scene_mesh builds (host code, no device) -> (nodes as a BVH_NODE_DTYPE array,
+    node 0 the root; order: the original index of every position of the leaf order -- triangles of zero area are in no leaf)."""
+    t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    nodes = np.zeros(max(1, t.size), BVH_NODE_DTYPE)
+    order = np.zeros(max(1, t.size), np.int32)
+    kept = C.c_int(0)
+    got = load_library().ptmi_mesh_layout(_ptr(t) if t.size else None, t.size, _ptr(nodes), nodes.size, _ptr(order) if t.size else None,
+                                          C.byref(kept))
+    if got < 0:
+        raise PtmiError(got, "ptmi_mesh_layout")
+    return nodes[:got].copy(), order[:kept.value].copy()
+
+
+def _mesh_args(spheres, triangles, planes):
+    s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE).reshape(-1)
+    return (s, t, p), (_ptr(s) if s.size else None, s.size, _ptr(t) if t.size else None, t.size, _ptr(p) if p.size else None, p.size)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(_vp)
 
@@ -246,6 +271,13 @@ class Context:
         p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
         self._check(self._lib.ptmi_set_scene_bvh(self._h, _ptr(s) if s.size else None, s.size,
                                                  _ptr(p) if p.size else None, p.size))
+
+    def set_scene_mesh(self, spheres, triangles, planes):
+        """ptmi_set_scene_mesh: spheres and planes as set_scene_bvh, plus triangles (TRIANGLE_DTYPE, up to MAX_MESH_TRIANGLES) through a
+        second hierarchy; triangle k is primitive len(spheres) + len(planes) + k."""
+        keep, args = _mesh_args(spheres, triangles, planes)
+        self._check(self._lib.ptmi_set_scene_mesh(self._h, *args))
+        del keep
 
     def set_partition(self, stripe_rows, n_parts, part):
         self._check(self._lib.ptmi_set_partition(self._h, stripe_rows, n_parts, part))
@@ -523,6 +555,11 @@ class Group:
         s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
         p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
         self._check(self._lib.ptmi_group_set_scene_bvh(self._h, _ptr(s) if s.size else None, s.size, _ptr(p) if p.size else None, p.size))
+
+    def set_scene_mesh(self, spheres, triangles, planes):
+        keep, args = _mesh_args(spheres, triangles, planes)
+        self._check(self._lib.ptmi_group_set_scene_mesh(self._h, *args))
+        del keep
 
     def resize(self, width, height):
         self._check(self._lib.ptmi_group_resize(self._h, width, height))

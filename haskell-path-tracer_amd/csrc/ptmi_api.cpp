@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ptmi_bvh.h"
+#include "ptmi_mesh.h"
 #include "ptmi_kernels.h"
 #include "ptmi_stage.h"
 
@@ -56,6 +57,11 @@ struct ptmi_ctx {
     bool scene_bvh = false;
     DeviceBlock d_bvh;
     BvhView bvh{};
+    // a mesh scene (ptmi_set_scene_mesh): d_scene with the triangles' materials too, the sphere hierarchy in d_bvh (bvh), and the
+    // triangle hierarchy -- nodes, the records in leaf order, their indices, the records by index -- in d_mesh
+    bool scene_mesh = false;
+    DeviceBlock d_mesh;
+    MeshView mesh{};
 
     DeviceBlock d_live;      // unsigned long long
     DeviceBlock d_work;      // unsigned int
@@ -152,7 +158,7 @@ struct ptmi_ctx {
     // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
     template <class F> void each_block(F &&f)
     {
-        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
                                &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
                                &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
             f(*b);
@@ -201,7 +207,7 @@ int effective_seed_rule(const ptmi_ctx *c)
 bool uses_stream_form(const ptmi_ctx *c, int algorithm, int n_parts, int n_spp)
 {
     if (algorithm != PTMI_STREAMS) return false;
-    if (c->scene_bvh) return false;                      // (a BVH scene renders through the per-pixel kernels only)
+    if (c->scene_bvh || c->scene_mesh) return false;     // (a BVH or mesh scene renders through the per-pixel kernels only)
     if (c->opt_form == PTMI_FORM_STREAM || c->variant == kVariantStreamForm) return true;
     if (c->opt_form == PTMI_FORM_PIXEL) return false;
     return c->has_glass && n_parts > 1 && (n_spp < 0 || n_spp >= 256);
@@ -933,6 +939,8 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
     const BvhView *bvh = c->scene_bvh ? &c->bvh : nullptr;    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
     if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
         PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == kVariantStreamForm ? kVariantAuto : c->variant, c->stream));
+    } else if (algorithm == PTMI_INLINE && c->scene_mesh) {
+        PTMI_HIP(c, launch_render_inline_mesh(a, c->mesh, c->stream));
     } else if (algorithm == PTMI_INLINE) {
         PTMI_HIP(c, launch_render_inline(a, bvh, c->variant, c->stream));
     } else if (stream_form) {                              // rays travel through streams in HBM (PTMI_OPT_STREAMS_FORM; kVariantStreamForm)
@@ -942,7 +950,10 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
         const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
         if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
         a.tree_stack = c->tree_stack.as<float4>();
-        PTMI_HIP(c, launch_render_streams_tree(a, bvh, c->variant, c->stream));
+        if (c->scene_mesh) PTMI_HIP(c, launch_render_streams_tree_mesh(a, c->mesh, c->stream));
+        else PTMI_HIP(c, launch_render_streams_tree(a, bvh, c->variant, c->stream));
+    } else if (c->scene_mesh) {
+        PTMI_HIP(c, launch_render_streams_mesh(a, c->mesh, c->stream));
     } else {
         PTMI_HIP(c, launch_render_streams(a, bvh, c->variant, c->stream));
     }
@@ -969,6 +980,8 @@ int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int
         return fail(c, PTMI_EINVAL, "PTMI_SEED_FROM_RESULT is undefined when rays split (GLASS): several results race for one pixel's seed");
     if (c->scene_bvh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
         return fail(c, PTMI_EINVAL, "a BVH scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
+    if (c->scene_mesh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+        return fail(c, PTMI_EINVAL, "a mesh scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
     return PTMI_OK;
 }
 
@@ -1255,8 +1268,10 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     if (e != hipSuccess) { release(fresh); PTMI_HIP(c, e); }
     release(c->d_scene);
     release(c->d_bvh);
+    release(c->d_mesh);
     c->d_scene = fresh;
     c->scene_bvh = false; c->bvh = BvhView{};
+    c->scene_mesh = false; c->mesh = MeshView{};
     c->n_spheres = n_spheres; c->n_planes = n_planes;
     ++c->scene_version;
     c->has_glass = false;
@@ -1310,9 +1325,11 @@ int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, c
     if (e != hipSuccess) { release(fresh); release(fresh_bvh); PTMI_HIP(c, e); }
     release(c->d_scene);
     release(c->d_bvh);
+    release(c->d_mesh);
     c->d_scene = fresh;
     c->d_bvh = fresh_bvh;
     c->scene_bvh = true;
+    c->scene_mesh = false; c->mesh = MeshView{};
     const float4 *base = c->d_bvh.as<float4>();
     c->bvh.nodes = base;
     c->bvh.geom = base + nodes_f4;
@@ -1323,6 +1340,113 @@ int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, c
     c->has_glass = false;
     for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
     for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    return PTMI_OK;
+#endif
+}
+
+int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
+                        const ptmi_plane *planes, int n_planes)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+#ifdef PTMI_ABLATIONS
+    (void)spheres; (void)n_spheres; (void)triangles; (void)n_triangles; (void)planes; (void)n_planes;
+    return fail(c, PTMI_EINVAL, "the ablation library has no mesh kernels: use libptmi for mesh scenes");
+#else
+    if (n_spheres < 0 || n_planes < 0 || n_triangles < 0 || (n_spheres > 0 && !spheres) || (n_planes > 0 && !planes) ||
+        (n_triangles > 0 && !triangles))
+        return fail(c, PTMI_EINVAL, "bad scene arguments");
+    if ((long long)n_spheres + n_planes + n_triangles == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
+    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
+    if (n_planes > PTMI_MAX_BVH_PLANES) return fail(c, PTMI_ELIMIT, "more planes than PTMI_MAX_BVH_PLANES");
+    if (n_triangles > PTMI_MAX_MESH_TRIANGLES) return fail(c, PTMI_ELIMIT, "more triangles than PTMI_MAX_MESH_TRIANGLES");
+    if (c->variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
+    if (c->opt_form == PTMI_FORM_STREAM)
+        return fail(c, PTMI_EINVAL, "a mesh scene has no stream form: set PTMI_OPT_STREAMS_FORM to PTMI_FORM_AUTO or PTMI_FORM_PIXEL first");
+    if (c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+        return fail(c, PTMI_EINVAL, "a mesh scene has no contracted-arithmetic kernel: set PTMI_OPT_ARITHMETIC back first");
+    for (int i = 0; i < n_spheres; ++i)
+        if (spheres[i].brdf_tag < PTMI_MATTE || spheres[i].brdf_tag > PTMI_GLASS)
+            return fail(c, PTMI_EINVAL, "sphere with unknown brdf_tag");
+    for (int j = 0; j < n_planes; ++j)
+        if (planes[j].brdf_tag < PTMI_MATTE || planes[j].brdf_tag > PTMI_GLASS)
+            return fail(c, PTMI_EINVAL, "plane with unknown brdf_tag");
+    for (int k = 0; k < n_triangles; ++k)
+        if (triangles[k].brdf_tag < PTMI_MATTE || triangles[k].brdf_tag > PTMI_GLASS)
+            return fail(c, PTMI_EINVAL, "triangle with unknown brdf_tag");
+    BvhBuild bb;
+    MeshBuild mb;
+    std::string why;
+    if (int rc = bvh_build(spheres, n_spheres, bb, &why)) return fail(c, rc, why);
+    if (int rc = mesh_build(triangles, n_triangles, mb, &why)) return fail(c, rc, why);
+    PTMI_HIP(c, hipSetDevice(c->device));
+    // d_scene: pack_scene's spheres and planes, then the materials of spheres, planes and triangles (primitive ns + np + k)
+    std::vector<float4> packed;
+    pack_scene(spheres, n_spheres, planes, n_planes, packed);
+    packed.reserve(packed.size() + 2 * (size_t)n_triangles);
+    for (int k = 0; k < n_triangles; ++k) {
+        const ptmi_triangle &t = triangles[k];
+        const float p = t.brdf_param;
+        packed.push_back(float4{t.color[0], t.color[1], t.color[2], t.illuminance});
+        packed.push_back(float4{u2f((uint32_t)t.brdf_tag), p, p / kPi, 0.5f * (1.0f - p)});
+    }
+    // d_bvh: as ptmi_set_scene_bvh makes it
+    const size_t nodes_f4 = bb.nodes.size() * 4, geom_f4 = (size_t)n_spheres;
+    std::vector<float4> hier(nodes_f4 + geom_f4 + ((size_t)n_spheres + 3) / 4);
+    std::memcpy(hier.data(), bb.nodes.data(), bb.nodes.size() * sizeof(ptmi_bvh_node));
+    for (int k = 0; k < n_spheres; ++k) hier[nodes_f4 + (size_t)k] = packed[(size_t)bb.order[(size_t)k]];
+    if (n_spheres > 0) std::memcpy(&hier[nodes_f4 + geom_f4], bb.order.data(), (size_t)n_spheres * sizeof(int32_t));
+    // d_mesh: the triangle nodes (four float4 each), the kept triangles in leaf order (three float4 each), their original indices, and
+    // every triangle by original index (three float4 each)
+    const size_t kept = mb.order.size();
+    const size_t tn_f4 = mb.nodes.size() * 4, tg_f4 = 3 * kept, ti_f4 = (kept + 3) / 4, tb_f4 = 3 * (size_t)n_triangles;
+    std::vector<float4> tri(tn_f4 + tg_f4 + ti_f4 + tb_f4);
+    std::memcpy(tri.data(), mb.nodes.data(), mb.nodes.size() * sizeof(ptmi_bvh_node));
+    for (size_t k = 0; k < kept; ++k)
+        std::memcpy(&tri[tn_f4 + 3 * k], &mb.records[(size_t)mb.order[k] * 12], 12 * sizeof(float));
+    if (kept > 0) std::memcpy(&tri[tn_f4 + tg_f4], mb.order.data(), kept * sizeof(int32_t));
+    if (n_triangles > 0) std::memcpy(&tri[tn_f4 + tg_f4 + ti_f4], mb.records.data(), (size_t)n_triangles * 12 * sizeof(float));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    // all three blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
+    DeviceBlock fresh, fresh_bvh, fresh_mesh;
+    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
+    hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_mesh, tri.size() * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_mesh.p, tri.data(), fresh_mesh.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier` and `tri` die at return
+    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); PTMI_HIP(c, e); }
+    release(c->d_scene);
+    release(c->d_bvh);
+    release(c->d_mesh);
+    c->d_scene = fresh;
+    c->d_bvh = fresh_bvh;
+    c->d_mesh = fresh_mesh;
+    c->scene_bvh = false;
+    c->scene_mesh = true;
+    const float4 *base = c->d_bvh.as<float4>();
+    c->bvh = BvhView{};
+    c->bvh.nodes = base;
+    c->bvh.geom = base + nodes_f4;
+    c->bvh.index = reinterpret_cast<const int *>(base + nodes_f4 + geom_f4);
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
+    const float4 *tb = c->d_mesh.as<float4>();
+    c->mesh = MeshView{};
+    c->mesh.spheres = c->bvh;
+    c->mesh.nodes = tb;
+    c->mesh.geom = tb + tn_f4;
+    c->mesh.index = reinterpret_cast<const int *>(tb + tn_f4 + tg_f4);
+    c->mesh.by_index = tb + tn_f4 + tg_f4 + ti_f4;
+    c->mesh.n_triangles = n_triangles;
+    c->mesh.n_kept = (int)kept;
+    for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = mb.lo[a]; c->mesh.hi[a] = mb.hi[a]; }
+    c->n_spheres = n_spheres; c->n_planes = n_planes;
+    ++c->scene_version;
+    c->has_glass = false;
+    for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
+    for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    for (int k = 0; k < n_triangles; ++k) c->has_glass |= triangles[k].brdf_tag == PTMI_GLASS;
     return PTMI_OK;
 #endif
 }
@@ -1438,6 +1562,7 @@ int ptmi_set_variant(ptmi_ctx *c, int variant)
     if (variant < 0 || variant >= kVariantCount) return fail(c, PTMI_EINVAL, "unknown variant");
     if (!variant_available(variant)) return fail(c, PTMI_EINVAL, "this variant is an ablation kernel: build libptmi with -DPTMI_ABLATIONS");
     if (c->scene_bvh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
+    if (c->scene_mesh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels only (variant 0)");
     c->variant = variant;
     return PTMI_OK;
 }
@@ -1499,6 +1624,7 @@ int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
     case PTMI_OPT_STREAMS_FORM:
         if (value != PTMI_FORM_AUTO && value != PTMI_FORM_STREAM && value != PTMI_FORM_PIXEL) return fail(c, PTMI_EINVAL, "unknown Streams form");
         if (c->scene_bvh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a BVH scene has no stream form (PTMI_FORM_STREAM)");
+        if (c->scene_mesh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a mesh scene has no stream form (PTMI_FORM_STREAM)");
         c->opt_form = (int)value; return PTMI_OK;
     case PTMI_OPT_STREAM_BATCH:
         if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "stream batch must be in [0, 64] samples");
@@ -1978,7 +2104,8 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     PTMI_HIP(c, hipMemcpyAsync(d_rays, rays, nb * 6 * 4, hipMemcpyHostToDevice, c->stream));
     SceneView scene;
     scene.packed = c->d_scene.as<float4>(); scene.n_spheres = c->n_spheres; scene.n_planes = c->n_planes;
-    PTMI_HIP(c, launch_eval_check_hit(scene, c->scene_bvh ? &c->bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
+    if (c->scene_mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(scene, c->mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
+    else PTMI_HIP(c, launch_eval_check_hit(scene, c->scene_bvh ? &c->bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(t_out, d_t, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(idx_out, d_idx, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(just_out, d_just, nb * 4, hipMemcpyDeviceToHost, c->stream));

@@ -211,6 +211,16 @@ int ptmi_group_set_scene_bvh(ptmi_group *g, const ptmi_sphere *spheres, int n_sp
     return PTMI_OK;
 }
 
+int ptmi_group_set_scene_mesh(ptmi_group *g, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
+                              const ptmi_plane *planes, int n_planes)
+{
+    if (!g) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(g->mu);
+    for (size_t i = 0; i < g->members.size(); ++i)
+        if (int rc = ptmi_set_scene_mesh(g->members[i], spheres, n_spheres, triangles, n_triangles, planes, n_planes)) return member_fail(g, (int)i, rc);
+    return PTMI_OK;
+}
+
 int ptmi_group_resize(ptmi_group *g, int width, int height)
 {
     if (!g) return PTMI_EINVAL;

@@ -15,7 +15,7 @@
 // ptmi_inline_ablations.hip, which only builds with -DPTMI_ABLATIONS.
 // This unit is compiled a second time with -DPTMI_CONTRACTED_BUILD -ffp-contract=fast -Dptmi=ptmi_contracted (a * b + c fused: a
 // labelled measurement mode, see the end of the file).
-#include "ptmi_bvh_device.h"
+#include "ptmi_mesh_device.h"
 
 namespace ptmi {
 
@@ -33,7 +33,11 @@ template <bool LDS_SCENE, int TILE_W = 0>
 __global__ void __launch_bounds__(kRenderBlock, PTMI_INLINE_WAVES) render_inline_kernel(const RenderArgs a)
 {
 #define PTMI_HIT(STAGED, ...) check_hit<STAGED>(__VA_ARGS__)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 #include "ptmi_inline_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 
@@ -45,7 +49,26 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_inline_bv
 {
     constexpr bool LDS_SCENE = false;
 #define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_bvh(bvh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 #include "ptmi_inline_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
+#undef PTMI_HIT
+}
+
+// mesh scenes (ptmi_set_scene_mesh): the same body, spheres ++ planes ++ triangles searched through the two hierarchies (check_hit_mesh),
+// a triangle's hit record from its stored normal
+template <int TILE_W>
+__global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_inline_mesh_kernel(const RenderArgs a, const MeshView mesh)
+{
+    constexpr bool LDS_SCENE = false;
+#define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_mesh(mesh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD(S, ns, idx, o, d, t, p, n) mesh_hit_record(mesh, S, ns, np, idx, o, d, t, p, n)
+#define PTMI_NORMAL_AT(S, ns, idx, p) mesh_normal_at(mesh, S, ns, np, idx, p)
+#include "ptmi_inline_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 #endif
@@ -100,6 +123,11 @@ hipError_t launch_render_inline(const RenderArgs &a, const BvhView *bvh, int var
 }
 
 #ifndef PTMI_CONTRACTED_BUILD
+hipError_t launch_render_inline_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream)
+{
+    return launch_per_pixel(a, Mapping::kAuto, render_inline_mesh_kernel<8>, render_inline_mesh_kernel<0>, false, PTMI_BVH_WAVES, 16, stream, mesh);
+}
+
 bool variant_available(int variant)
 {
     switch (variant) {

@@ -1,5 +1,7 @@
-// ptmi_inline_body.inc -- the body of render_inline_kernel, shared by the kernel of linear scenes and render_inline_bvh_kernel (BVH scenes).
-// Included INSIDE the kernels (ptmi_inline.hip), which define PTMI_HIT(STAGED, S, ns, np, o, d[, diag]) -- the hit search -- and, for the BVH
+// ptmi_inline_body.inc -- the body of render_inline_kernel, shared by the kernel of linear scenes and render_inline_bvh_kernel (BVH scenes) and
+// render_inline_mesh_kernel (mesh scenes).
+// Included INSIDE the kernels (ptmi_inline.hip), which define PTMI_HIT(STAGED, S, ns, np, o, d[, diag]) -- the hit search --, PTMI_HIT_RECORD and PTMI_NORMAL_AT (hit_record and
+// normal_at, or a mesh scene's) and, for the BVH and mesh
 // kernel, LDS_SCENE = false.  (A __device__ function for the body changes the code the compiler makes of the linear kernels; the
 // text shared this way leaves them instruction for instruction as they were: tools/isa_diff.py.)
     __shared__ float pixel_const[10][kRenderBlock];         // per-lane restart record (see below)
@@ -68,7 +70,7 @@
                 auto put = [&](int k, float v) { mine[k * kRenderBlock] = v; };
                 auto get = [&](int k) { return mine[k * kRenderBlock]; };
                 V3 pos, normal;                                       // pos: the hit to shade, then the next ray's origin
-                hit_record(S, ns, h0.idx, origin, primary, h0.t, pos, normal);
+                PTMI_HIT_RECORD(S, ns, h0.idx, origin, primary, h0.t, pos, normal);
                 const int idx0 = h0.idx;
                 {
                     const float4 mb0 = M[2 * idx0 + 1];
@@ -127,7 +129,7 @@
                         const HitSel h = PTMI_HIT(LDS_SCENE, S, ns, np, pos, d, diag::sphere_counters(a.work_counter));
                         has_ray = false;
                         if (h.just) {
-                            hit_record(S, ns, h.idx, pos, d, h.t, pos, normal);
+                            PTMI_HIT_RECORD(S, ns, h.idx, pos, d, h.t, pos, normal);
                             idx = h.idx;
                             pending = true;
                         } else {

@@ -37,6 +37,18 @@ struct BvhView {
     float lo[3], hi[3];       // box of the sphere centres
 };
 
+// A mesh scene (ptmi_set_scene_mesh; ptmi_mesh_device.h walks it): a BVH scene's spheres and planes, and the triangles in a second
+// hierarchy.  The packed scene holds the materials of spheres, planes AND triangles (triangle k is primitive ns + np + k).
+struct MeshView {
+    BvhView spheres;          // the sphere hierarchy, as for a BVH scene
+    const float4 *nodes;      // the triangle hierarchy, ptmi_bvh_node as above (inv_2r unused)
+    const float4 *geom;       // the triangles in leaf order, three float4 each: (v0, nx) (v1, ny) (v2, nz), n the unit normal
+    const int *index;         // ... and their original indices
+    const float4 *by_index;   // the same records by original index (zero area: a NaN normal, never hit)
+    int n_triangles, n_kept;  // all of them / those in the hierarchy (non-zero area)
+    float lo[3], hi[3];       // box of the kept triangles' vertices
+};
+
 struct Planes {
     float *r, *g, *b;
     uint32_t *sa, *sb, *sc, *sctr;
@@ -243,6 +255,11 @@ hipError_t launch_render_inline_ablation(const RenderArgs &a, int variant, bool 
 hipError_t launch_render_streams(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream);
 hipError_t launch_render_streams_tree(const RenderArgs &a, const BvhView *bvh, int variant, hipStream_t stream);   // scenes with GLASS: per-pixel tree walk
 hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
+// ... their mesh-scene instantiations (ptmi_set_scene_mesh: variant 0, per-pixel forms only)
+hipError_t launch_render_inline_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
+hipError_t launch_render_streams_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
+hipError_t launch_render_streams_tree_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
+hipError_t launch_eval_check_hit_mesh(SceneView scene, const MeshView &mesh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

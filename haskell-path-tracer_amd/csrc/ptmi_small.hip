@@ -1,7 +1,7 @@
 // ptmi_small.hip -- the HBM-streaming kernels around the render kernels: genSeeds / createWith / initialOutput / reseed
 // (src/Util.hs:122-135, 204-205), present (app/Main.hs:351, app/assets/fs.glsl:12), the group read-out's stitch, the cost order of
 // the tiled kernels' dispatch, and the point queries behind the reference's unit-test surface (test/Scene/Intersection/Tests.hs).
-#include "ptmi_bvh_device.h"
+#include "ptmi_mesh_device.h"
 
 namespace ptmi {
 
@@ -140,6 +140,20 @@ __global__ void __launch_bounds__(kRenderBlock) eval_check_hit_kernel(const Scen
     idx_out[i] = h.just ? h.idx : -1;
 }
 
+// ... over a mesh scene (check_hit_mesh)
+__global__ void __launch_bounds__(kRenderBlock) eval_check_hit_mesh_kernel(const SceneView scene, const MeshView mesh, const float *rays, int n,
+                                                                           float *t_out, int32_t *idx_out, int32_t *just_out)
+{
+    const int i = blockIdx.x * kRenderBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
+    const V3 d = mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
+    const HitSel h = check_hit_mesh(mesh, scene.packed, scene.n_spheres, scene.n_planes, o, d);
+    just_out[i] = h.just ? 1 : 0;
+    t_out[i] = h.just ? h.t : 0.0f;
+    idx_out[i] = h.just ? h.idx : -1;
+}
+
 __global__ void __launch_bounds__(kBlock) eval_plane_kernel(const float *pl, const float *rays, int n,
                                                             int32_t *is_just, float *t_out, float *normalp)
 {
@@ -262,6 +276,12 @@ hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const floa
     const dim3 grid(blocks_for(n, kRenderBlock)), block(kRenderBlock);
     if (bvh) return launch(eval_check_hit_kernel<true>, grid, block, 0, stream, scene, *bvh, rays, n, t, idx, just);
     return launch(eval_check_hit_kernel<false>, grid, block, 0, stream, scene, BvhView{}, rays, n, t, idx, just);
+}
+
+hipError_t launch_eval_check_hit_mesh(SceneView scene, const MeshView &mesh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    return launch(eval_check_hit_mesh_kernel, dim3(blocks_for(n, kRenderBlock)), dim3(kRenderBlock), 0, stream, scene, mesh, rays, n, t, idx, just);
 }
 
 hipError_t launch_eval_plane(const float *planes12, const float *rays, int n,

@@ -1,6 +1,6 @@
 // ptmi_streams_chain.hip -- render Streams (src/Scene/Trace.hs:141-191, 272-331), one chain per pixel: the default of Streams for
 // every scene whose rays never split, and the per-pixel TAIL of the stream form (ptmi_stream_pixels.hip).
-#include "ptmi_bvh_device.h"
+#include "ptmi_mesh_device.h"
 
 namespace ptmi {
 
@@ -32,7 +32,11 @@ template <bool LDS_SCENE, int TILE_W = 0>
 __global__ void __launch_bounds__(kRenderBlock, PTMI_STREAMS_WAVES) render_streams_kernel(const RenderArgs a)
 {
 #define PTMI_HIT(STAGED, ...) check_hit<STAGED>(__VA_ARGS__)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 #include "ptmi_streams_chain_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 
@@ -43,7 +47,25 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_streams_b
 {
     constexpr bool LDS_SCENE = false;
 #define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_bvh(bvh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 #include "ptmi_streams_chain_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
+#undef PTMI_HIT
+}
+
+// mesh scenes (ptmi_set_scene_mesh): the same body, spheres ++ planes ++ triangles searched through the two hierarchies (check_hit_mesh)
+template <int TILE_W>
+__global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_streams_mesh_kernel(const RenderArgs a, const MeshView mesh)
+{
+    constexpr bool LDS_SCENE = false;
+#define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_mesh(mesh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD(S, ns, idx, o, d, t, p, n) mesh_hit_record(mesh, S, ns, np, idx, o, d, t, p, n)
+#define PTMI_NORMAL_AT(S, ns, idx, p) mesh_normal_at(mesh, S, ns, np, idx, p)
+#include "ptmi_streams_chain_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 
@@ -63,6 +85,12 @@ hipError_t launch_render_streams(const RenderArgs &a, const BvhView *bvh, int va
     const bool rows = variant == kVariantRows || variant == kVariantRowsScalar;          // 4 / 5 keep the row mapping (ablation)
     const bool scalar = variant == kVariantRowsScalar || variant == kVariantPersistentScalar || variant == kVariantTilesScalar;
     return launch_linear(a, rows ? Mapping::kRows : Mapping::kAuto, !scalar && scene_fits_lds(a), stream);
+}
+
+hipError_t launch_render_streams_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream)
+{
+    if (hipError_t e = clear_stream_iterations(a, stream)) return e;
+    return launch_per_pixel(a, Mapping::kAuto, render_streams_mesh_kernel<8>, render_streams_mesh_kernel<0>, false, PTMI_BVH_WAVES, 16, stream, mesh);
 }
 
 // The per-pixel chain kernel as the TAIL of a stream-form launch: a grid over every dispatch position whose workgroups start at

@@ -1,6 +1,6 @@
 // ptmi_streams_tree.hip -- render Streams for scenes whose rays SPLIT (the build-defined GLASS extension), per-pixel form: the
 // tree walk (the default with GLASS).  The stream form of the same algorithm is ptmi_stream_split.hip.
-#include "ptmi_bvh_device.h"
+#include "ptmi_mesh_device.h"
 
 namespace ptmi {
 
@@ -34,6 +34,8 @@ template <bool LDS_SCENE, int TILE_W = 0>
 __global__ void __launch_bounds__(kRenderBlock, PTMI_TREE_WAVES) render_streams_tree_kernel(const RenderArgs a)
 {
 #define PTMI_HIT(STAGED, ...) check_hit<STAGED>(__VA_ARGS__)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 // a linear scene has at most PTMI_MAX_PRIMITIVES = 1024 primitives: 16 bits of primitive, steps at bit 16, draws at bit 24
 #define PTMI_TREE_PACK(prim, steps, draws) ((uint32_t)(prim) | ((steps) << 16) | ((draws) << 24))
 #define PTMI_TREE_PRIM(w) ((w) & 0xffffu)
@@ -42,6 +44,8 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_TREE_WAVES) render_streams_
 #undef PTMI_TREE_PACK
 #undef PTMI_TREE_PRIM
 #undef PTMI_TREE_META
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 
@@ -52,6 +56,8 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_streams_t
 {
     constexpr bool LDS_SCENE = false;
 #define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_bvh(bvh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
 // a BVH scene has up to PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES primitives: 24 bits of primitive, steps at bit 24, draws at bit 25
 static_assert(PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES <= (1 << 24), "the tree walk's start record holds 24 bits of primitive");
 #define PTMI_TREE_PACK(prim, steps, draws) ((uint32_t)(prim) | ((steps) << 24) | ((draws) << 25))
@@ -61,6 +67,30 @@ static_assert(PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES <= (1 << 24), "the tree
 #undef PTMI_TREE_PACK
 #undef PTMI_TREE_PRIM
 #undef PTMI_TREE_META
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
+#undef PTMI_HIT
+}
+
+// mesh scenes (ptmi_set_scene_mesh): the same body, spheres ++ planes ++ triangles searched through the two hierarchies (check_hit_mesh)
+template <int TILE_W>
+__global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_streams_tree_mesh_kernel(const RenderArgs a, const MeshView mesh)
+{
+    constexpr bool LDS_SCENE = false;
+#define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit_mesh(mesh, S, ns, np, o, d)
+#define PTMI_HIT_RECORD(S, ns, idx, o, d, t, p, n) mesh_hit_record(mesh, S, ns, np, idx, o, d, t, p, n)
+#define PTMI_NORMAL_AT(S, ns, idx, p) mesh_normal_at(mesh, S, ns, np, idx, p)
+// up to PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES + PTMI_MAX_MESH_TRIANGLES primitives: the BVH kernel's 24 bits of primitive
+static_assert(PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES + PTMI_MAX_MESH_TRIANGLES <= (1 << 24), "the tree walk's start record holds 24 bits of primitive");
+#define PTMI_TREE_PACK(prim, steps, draws) ((uint32_t)(prim) | ((steps) << 24) | ((draws) << 25))
+#define PTMI_TREE_PRIM(w) ((w) & 0xffffffu)
+#define PTMI_TREE_META(w) ((((w) >> 24) & 1u) | (((w) >> 25) << 8))
+#include "ptmi_streams_tree_body.inc"
+#undef PTMI_TREE_PACK
+#undef PTMI_TREE_PRIM
+#undef PTMI_TREE_META
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
 #undef PTMI_HIT
 }
 
@@ -83,6 +113,12 @@ hipError_t launch_render_streams_tree(const RenderArgs &a, const BvhView *bvh, i
     if (variant != kVariantRowsScalar && variant != kVariantTilesScalar && scene_fits_lds(a))
         return launch_per_pixel(a, mapping, render_streams_tree_kernel<true, 8>, render_streams_tree_kernel<true>, true, PTMI_TREE_WAVES, 10, stream);
     return launch_per_pixel(a, mapping, render_streams_tree_kernel<false, 8>, render_streams_tree_kernel<false>, false, PTMI_TREE_WAVES, 10, stream);
+}
+
+hipError_t launch_render_streams_tree_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream)
+{
+    if (hipError_t e = clear_stream_iterations(a, stream)) return e;
+    return launch_per_pixel(a, Mapping::kAuto, render_streams_tree_mesh_kernel<8>, render_streams_tree_mesh_kernel<0>, false, PTMI_BVH_WAVES, 10, stream, mesh);
 }
 
 }  // namespace ptmi

@@ -1,7 +1,9 @@
-// ptmi_streams_tree_body.inc -- the body of render_streams_tree_kernel, shared by the kernel of linear scenes and render_streams_tree_bvh_kernel (BVH scenes).
-// Included INSIDE the kernels (ptmi_streams_tree.hip), which define the hit search PTMI_HIT(STAGED, S, ns, np, o, d[, diag]); the start
+// ptmi_streams_tree_body.inc -- the body of render_streams_tree_kernel, shared by the kernel of linear scenes and render_streams_tree_bvh_kernel (BVH scenes) and
+// render_streams_tree_mesh_kernel (mesh scenes).
+// Included INSIDE the kernels (ptmi_streams_tree.hip), which define the hit search PTMI_HIT(STAGED, S, ns, np, o, d[, diag]), PTMI_HIT_RECORD and PTMI_NORMAL_AT
+// (hit_record and normal_at, or a mesh scene's); the start
 // record's word of primitive, steps (0 or 1) and draws (0 or 1): PTMI_TREE_PACK(prim, steps, draws), PTMI_TREE_PRIM(word) and
-// PTMI_TREE_META(word) = steps | draws << 8 (16 bits of primitive for linear scenes, 24 for BVH scenes); and, for the BVH kernel,
+// PTMI_TREE_META(word) = steps | draws << 8 (16 bits of primitive for linear scenes, 24 for BVH and mesh scenes); and, for the BVH and mesh kernels,
 // LDS_SCENE = false.  (A __device__ function for the body changes the code the compiler makes of the linear kernels; the text shared
 // this way leaves them instruction for instruction as they were: tools/isa_diff.py.)
     // two start hits per lane: position (3), incoming direction (3), throughput (3), primitive, steps and draws in one word (PTMI_TREE_PACK)
@@ -58,7 +60,7 @@
                 if (PTMI_TREE_NORMAL_LDS) { q[10 * kRenderBlock] = f2u(nrm.x); q[11 * kRenderBlock] = f2u(nrm.y); q[12 * kRenderBlock] = f2u(nrm.z); }
             };
             V3 pos, normal;                                       // pos: the hit to shade, then the next ray's origin
-            hit_record(S, ns, h0.idx, origin, primary, h0.t, pos, normal);
+            PTMI_HIT_RECORD(S, ns, h0.idx, origin, primary, h0.t, pos, normal);
             int n_entries = 0;
             bool first_is_reflection = false;
             V3 emit0 = mk(0.0f, 0.0f, 0.0f);
@@ -77,7 +79,7 @@
                     const HitSel h = PTMI_HIT(LDS_SCENE && kStagedWalk, S, ns, np, ro, rd);
                     if (h.just) {
                         V3 hp, hn;
-                        hit_record(S, ns, h.idx, ro, rd, h.t, hp, hn);
+                        PTMI_HIT_RECORD(S, ns, h.idx, ro, rd, h.t, hp, hn);
                         if (n_entries == 0) first_is_reflection = k == 0;
                         put_entry(n_entries++, hp, hn, rd, rt, h.idx, 1u, (unsigned int)k);
                     }
@@ -125,7 +127,7 @@
                         const uint32_t meta = PTMI_TREE_META(q[9 * kRenderBlock]);
                         ++entry_i;
                         steps = meta & 0xffu;
-                        normal = PTMI_TREE_NORMAL_LDS ? mk(u2f(q[10 * kRenderBlock]), u2f(q[11 * kRenderBlock]), u2f(q[12 * kRenderBlock])) : normal_at(S, ns, idx, pos);
+                        normal = PTMI_TREE_NORMAL_LDS ? mk(u2f(q[10 * kRenderBlock]), u2f(q[11 * kRenderBlock]), u2f(q[12 * kRenderBlock])) : PTMI_NORMAL_AT(S, ns, idx, pos);
                         seed = pixel_seed;                        // (with a prefix: the lead seed -- the draws the ray's ancestors made)
                         if (meta >> 8) (void)sfc32_next(seed);    // the refraction child: one more
                         pending = true; has_ray = false;
@@ -247,7 +249,7 @@
                     const HitSel h = PTMI_HIT(LDS_SCENE && kStagedWalk, S, ns, np, pos, d);
                     has_ray = false;
                     if (h.just) {
-                        hit_record(S, ns, h.idx, pos, d, h.t, pos, normal);
+                        PTMI_HIT_RECORD(S, ns, h.idx, pos, d, h.t, pos, normal);
                         idx = h.idx;
                         pending = true;
                     } else {

@@ -44,7 +44,9 @@ struct Material { Color color; float illuminance; Brdf brdf; };    // Objects.hs
 struct Sphere { Point position; float radius; Material material; };        // Objects.hs:126-131
 struct Plane { Point position; Direction direction; Material material; };  // Objects.hs:103-108
 struct Camera { Point position; Direction rotation; int64_t fov; };        // Objects.hs:67-74
-struct SceneDescription { std::vector<Sphere> spheres; std::vector<Plane> planes; };   // Objects.hs:60-64
+struct Triangle { Point v0, v1, v2; Material material; };                  // extension (ptmi_triangle): no reference type
+// Objects.hs:60-64; triangles only for SceneKind::Mesh
+struct SceneDescription { std::vector<Sphere> spheres; std::vector<Plane> planes; std::vector<Triangle> triangles; };
 
 class PtmiError : public std::runtime_error {
 public:
@@ -152,9 +154,10 @@ constexpr int maxIterations = 15;                                        // Trac
 }  // namespace Trace
 
 // ---- the device context (what runN's backend state is to the reference) -------------------------
-// How the context holds the scene: Linear (ptmi_set_scene, up to PTMI_MAX_PRIMITIVES primitives) or Bvh (ptmi_set_scene_bvh: the
-// spheres in a bounding-volume hierarchy, up to PTMI_MAX_BVH_SPHERES; the same images, bit for bit).
-enum class SceneKind { Linear, Bvh };
+// How the context holds the scene: Linear (ptmi_set_scene, up to PTMI_MAX_PRIMITIVES primitives), Bvh (ptmi_set_scene_bvh: the
+// spheres in a bounding-volume hierarchy, up to PTMI_MAX_BVH_SPHERES; the same images, bit for bit) or Mesh (ptmi_set_scene_mesh: a
+// Bvh scene plus up to PTMI_MAX_MESH_TRIANGLES triangles in a second hierarchy, folded after the planes).
+enum class SceneKind { Linear, Bvh, Mesh };
 
 class Device {
 public:
@@ -183,7 +186,15 @@ public:
                                     {p.direction.x, p.direction.y, p.direction.z},
                                     {p.material.color.x, p.material.color.y, p.material.color.z},
                                     p.material.illuminance, p.material.brdf.tag, p.material.brdf.parameter});
-        if (kind == SceneKind::Bvh) check(ptmi_set_scene_bvh(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
+        if (kind != SceneKind::Mesh && !scene.triangles.empty()) throw PtmiError(PTMI_EINVAL, "triangles need SceneKind::Mesh");
+        if (kind == SceneKind::Mesh) {
+            std::vector<ptmi_triangle> tr;
+            for (const Triangle &t : scene.triangles)
+                tr.push_back(ptmi_triangle{{t.v0.x, t.v0.y, t.v0.z}, {t.v1.x, t.v1.y, t.v1.z}, {t.v2.x, t.v2.y, t.v2.z},
+                                           {t.material.color.x, t.material.color.y, t.material.color.z},
+                                           t.material.illuminance, t.material.brdf.tag, t.material.brdf.parameter});
+            check(ptmi_set_scene_mesh(ctx_.get(), sp.data(), (int)sp.size(), tr.data(), (int)tr.size(), pl.data(), (int)pl.size()));
+        } else if (kind == SceneKind::Bvh) check(ptmi_set_scene_bvh(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
         else check(ptmi_set_scene(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
     }
     ptmi_ctx *get() const { return ctx_.get(); }

@@ -16,7 +16,10 @@ SPHERE_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<
 PLANE_DTYPE = np.dtype([("position", "<f4", 3), ("direction", "<f4", 3), ("color", "<f4", 3),
                         ("illuminance", "<f4"), ("brdf_tag", "<i4"), ("brdf_param", "<f4")])
 CAMERA_DTYPE = np.dtype([("position", "<f4", 3), ("rotation", "<f4", 3), ("fov", "<i8")])
-assert SPHERE_DTYPE.itemsize == 40 and PLANE_DTYPE.itemsize == 48 and CAMERA_DTYPE.itemsize == 32
+# ptmi_triangle (extension: the reference has no triangle type): three vertices, counter-clockwise seen from the front, and a material
+TRIANGLE_DTYPE = np.dtype([("v0", "<f4", 3), ("v1", "<f4", 3), ("v2", "<f4", 3), ("color", "<f4", 3),
+                           ("illuminance", "<f4"), ("brdf_tag", "<i4"), ("brdf_param", "<f4")])
+assert SPHERE_DTYPE.itemsize == 40 and PLANE_DTYPE.itemsize == 48 and CAMERA_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 60
 
 
 def sphere(position, radius, color, illuminance, brdf_tag, brdf_param):
@@ -25,6 +28,10 @@ def sphere(position, radius, color, illuminance, brdf_tag, brdf_param):
 
 def plane(position, direction, color, illuminance, brdf_tag, brdf_param):
     return (tuple(position), tuple(direction), tuple(color), illuminance, brdf_tag, brdf_param)
+
+
+def triangle(v0, v1, v2, color, illuminance, brdf_tag, brdf_param):
+    return (tuple(v0), tuple(v1), tuple(v2), tuple(color), illuminance, brdf_tag, brdf_param)
 
 
 def initial_camera():
@@ -139,3 +146,116 @@ def sphere_field(n_spheres, seed=0, glass_fraction=0.0):
         plane((1.0 - 0.5 * w - 4.0, 0.0, 0.0), (1.0, 0.0, 0.0), (0.8, 0.5, 0.4), 0.0, GLOSSY, 0.7),
     ], dtype=PLANE_DTYPE)
     return s, planes
+
+
+def triangles_of(vertices, faces, material):
+    """TRIANGLE_DTYPE records for faces (k x 3 vertex indices into vertices, k x 3 floats) with one material (color, illuminance,
+    brdf_tag, brdf_param)."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    t = np.zeros(len(f), dtype=TRIANGLE_DTYPE)
+    t["v0"], t["v1"], t["v2"] = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    color, illuminance, brdf_tag, brdf_param = material
+    t["color"] = color
+    t["illuminance"] = illuminance
+    t["brdf_tag"] = brdf_tag
+    t["brdf_param"] = brdf_param
+    return t
+
+
+def load_obj(path_or_text, material):
+    """A minimal Wavefront OBJ reader: `v x y z` and `f a b c ...` lines only (1-based indices, negative ones counted back from the
+    last vertex read, `a/b/c` forms use the position index); polygons are fan-triangulated (a b c, a c d, ...); every other line is
+    ignored.  path_or_text: a file name, or the text itself when it holds a newline.  -> TRIANGLE_DTYPE records with `material`."""
+    text = path_or_text
+    if "\n" not in path_or_text:
+        with open(path_or_text) as fh:
+            text = fh.read()
+    verts, faces = [], []
+    for line in text.splitlines():
+        parts = line.split("#", 1)[0].split()
+        if not parts:
+            continue
+        if parts[0] == "v" and len(parts) >= 4:
+            verts.append([float(x) for x in parts[1:4]])
+        elif parts[0] == "f" and len(parts) >= 4:
+            idx = []
+            for p in parts[1:]:
+                k = int(p.split("/")[0])
+                idx.append(k - 1 if k > 0 else len(verts) + k)
+            if any(i < 0 or i >= len(verts) for i in idx):
+                raise ValueError("OBJ face refers to a vertex that does not exist: %r" % line)
+            for j in range(1, len(idx) - 1):
+                faces.append((idx[0], idx[j], idx[j + 1]))
+    return triangles_of(np.array(verts, np.float32).reshape(-1, 3), np.array(faces, np.int64).reshape(-1, 3), material)
+
+
+def icosphere(subdivisions):
+    """The unit icosphere: an icosahedron whose faces are split into 4 `subdivisions` times, vertices pushed onto the sphere; faces
+    counter-clockwise seen from outside.  20 * 4^subdivisions faces.  -> (vertices k x 3 float64, faces m x 3)"""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+         (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    verts = [np.array(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(int(subdivisions)):
+        mid, nf = {}, []
+
+        def m(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                p = verts[a] + verts[b]
+                verts.append(p / np.linalg.norm(p))
+                mid[key] = len(verts) - 1
+            return mid[key]
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    v, f = np.array(verts), np.array(f, np.int64)
+    n = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    inward = np.einsum("ij,ij->i", n, v[f[:, 0]]) < 0
+    f[inward] = f[inward][:, [0, 2, 1]]                 # counter-clockwise seen from outside
+    return v, f
+
+
+def mesh_room(subdivisions=2, n_spheres=8, seed=0):
+    """A closed room of triangles (12: floor, glowing ceiling, four walls, inward-facing) with an emissive triangle light under the ceiling,
+    n_spheres spheres inside, and an icosphere mesh of 20 * 4^subdivisions triangles (2 -> 320, 4 -> 5 120, 6 -> 81 920, 8 -> 1.3 M)
+    in front of initial_camera().  No planes.  For mesh scenes (ptmi_set_scene_mesh) -- tests and tools/mesh_bench.py.
+    -> (spheres, triangles, planes)"""
+    rng = np.random.default_rng(seed)
+    x0, x1, y0, y1, z0, z1 = -12.0, 14.0, -3.0, 15.0, -30.0, 8.0
+    c = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
+    # the six faces, each a quad (a, b, c, d), turned below to face into the room
+    quads = [((0, 1, 5, 4), (0.43, 0.95, 0.5), 0.0, MATTE, 1.0),        # floor (y0), normal +y
+             ((3, 7, 6, 2), (0.9, 0.9, 0.85), 2.0, MATTE, 1.0),         # ceiling (y1), normal -y, glowing
+             ((0, 3, 2, 1), (0.9, 0.9, 0.9), 0.0, MATTE, 1.0),          # back (z0), normal +z
+             ((4, 5, 6, 7), (0.8, 0.8, 0.8), 0.0, MATTE, 0.8),          # front (z1), normal -z
+             ((0, 4, 7, 3), (0.8, 0.5, 0.4), 0.0, GLOSSY, 0.7),         # left (x0), normal +x
+             ((1, 2, 6, 5), (0.4, 0.5, 0.8), 0.0, MATTE, 0.9)]          # right (x1), normal -x
+    tris = []
+    for (a, b, cc, d), col, il, tag, p in quads:
+        tris.append(triangle(c[a], c[b], c[cc], col, il, tag, p))
+        tris.append(triangle(c[a], c[cc], c[d], col, il, tag, p))
+    centre = np.array([(x0 + x1) / 2, (y0 + y1) / 2, (z0 + z1) / 2])
+    for k, (v0, v1, v2, *rest) in enumerate(tris):             # every wall faces into the room
+        n = np.cross(np.subtract(v1, v0), np.subtract(v2, v0))
+        if np.dot(n, centre - np.array(v0)) < 0:
+            tris[k] = (v0, v2, v1, *rest)
+    # the light: one triangle facing down, just under the ceiling
+    tris.append(triangle((-2.0, 14.5, -14.0), (4.0, 14.5, -14.0), (1.0, 14.5, -8.0), (1.0, 0.95, 0.9), 40.0, MATTE, 1.0))
+    room = np.array(tris, dtype=TRIANGLE_DTYPE)
+    v, f = icosphere(subdivisions)
+    mesh = triangles_of(v * 3.0 + np.array([1.0, 3.0, -16.0]), f, ((0.85, 0.75, 0.4), 0.0, GLOSSY, 0.8))
+    s = np.zeros(int(n_spheres), dtype=SPHERE_DTYPE)
+    s["position"][:, 0] = -8.0 + 18.0 * rng.random(len(s))
+    s["position"][:, 1] = -2.0 + 6.0 * rng.random(len(s))
+    s["position"][:, 2] = -26.0 + 16.0 * rng.random(len(s))
+    s["radius"] = 0.5 + 0.8 * rng.random(len(s))
+    s["color"] = 0.2 + 0.75 * rng.random((len(s), 3))
+    s["illuminance"] = np.where(np.arange(len(s)) % 4 == 0, 30.0, 0.0)
+    s["brdf_tag"] = np.where(np.arange(len(s)) % 3 == 0, GLOSSY, MATTE)
+    s["brdf_param"] = 0.8
+    return s, np.concatenate([room, mesh]), np.zeros(0, dtype=PLANE_DTYPE)

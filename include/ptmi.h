@@ -41,7 +41,8 @@ extern "C" {
                             * capacity; option 13 and ptmi_stream_tickets; the stream form's overflow streams grow instead of dropping children;
                             * no option is read from the environment any more.  (0.4.0: options 8-12, ptmi_stream_schedule.)
                             * Added without a version bump: the bounding-volume-hierarchy scene (ptmi_set_scene_bvh, ptmi_group_set_scene_bvh,
-                            * ptmi_bvh_layout, ptmi_bvh_node, PTMI_MAX_BVH_*) and ptmi_eval_check_hit. */
+                            * ptmi_bvh_layout, ptmi_bvh_node, PTMI_MAX_BVH_*) and ptmi_eval_check_hit; the mesh scene (ptmi_set_scene_mesh,
+                            * ptmi_group_set_scene_mesh, ptmi_mesh_layout, ptmi_triangle, PTMI_MAX_MESH_TRIANGLES). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -73,6 +74,7 @@ enum { PTMI_MATTE = 0, PTMI_GLOSSY = 1, PTMI_GLASS = 2 };
 #define PTMI_MAX_BVH_PLANES  64          /* ... planes, folded linearly after the spheres */
 #define PTMI_BVH_MAX_DEPTH   24          /* levels of inner nodes (the root is level 0); the device keeps one stack entry per level */
 #define PTMI_BVH_LEAF_MAX    4           /* spheres per leaf */
+#define PTMI_MAX_MESH_TRIANGLES (1 << 22) /* ptmi_set_scene_mesh: triangles in the second hierarchy (spheres and planes as for BVH scenes) */
 
 /* ---- scene types: field order = src/Scene/Objects.hs ------------------------ */
 typedef struct ptmi_sphere {       /* data Sphere   Objects.hs:126-131, Material :90-100 */
@@ -105,6 +107,17 @@ typedef struct ptmi_bvh_node {
     int32_t ref[2];
     float   inv_2r[2];
 } ptmi_bvh_node;                   /* 16 words */
+
+/* A triangle (extension: the reference has no triangle type).  A bounded, one-sided plane: n = cross(v1 - v0, v2 - v0), the front is
+ * counter-clockwise; hit where the plane (v0, n / |n|) is hit (distanceTo @Plane) and the hit point lies inside or on the edges.  A
+ * triangle of zero area is never hit.  Material fields as in ptmi_sphere and ptmi_plane. */
+typedef struct ptmi_triangle {
+    float   v0[3], v1[3], v2[3];
+    float   color[3];
+    float   illuminance;
+    int32_t brdf_tag;
+    float   brdf_param;
+} ptmi_triangle;                   /* 15 words */
 
 typedef struct ptmi_camera {       /* data Camera   Objects.hs:67-74 */
     float   position[3];
@@ -173,6 +186,22 @@ int ptmi_set_scene_bvh(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres,
  * (node_capacity), `order` n_spheres.  Returns the number of nodes; PTMI_ELIMIT beyond PTMI_MAX_BVH_SPHERES or when node_capacity
  * is too small, PTMI_EINVAL for NULL pointers or non-finite sphere data. */
 int ptmi_bvh_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
+
+/* A MESH scene: a BVH scene (the spheres through ptmi_set_scene_bvh's hierarchy, the planes folded linearly) plus up to
+ * PTMI_MAX_MESH_TRIANGLES triangles in a second hierarchy (ptmi_mesh_layout).  checkHit folds over spheres ++ planes ++ triangles:
+ * triangle k is primitive n_spheres + n_planes + k, and every tie keeps the earlier primitive, so with no triangles the render is bit
+ * for bit the BVH scene's.  Fails with PTMI_ELIMIT beyond the limits (nothing at all: PTMI_EINVAL), with PTMI_EINVAL for non-finite
+ * sphere, vertex or material data or a normal whose square does not stay finite, and -- as ptmi_set_scene_bvh -- for the stream form,
+ * a variant other than 0 and the ablation library (PTMI_FORM_AUTO picks the per-pixel form); render Inline has no contracted
+ * kernel for it.  Transactional: after a failure the previous scene, of any kind, stays. */
+int ptmi_set_scene_mesh(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
+                        const ptmi_plane *planes, int n_planes);
+
+/* The triangle hierarchy ptmi_set_scene_mesh builds (pure host code, deterministic), in ptmi_bvh_node form: inv_2r is 0, each
+ * triangle's box is padded as DESIGN.md 5.8 says and order[k] is the original index of the triangle at position k of the leaf order.
+ * Triangles of zero area are in no leaf: the return value's order has n_kept entries (*n_kept, may be NULL).  `nodes` needs
+ * max(1, n_triangles) entries, `order` n_triangles.  Returns the number of nodes, or PTMI_ELIMIT / PTMI_EINVAL as ptmi_bvh_layout. */
+int ptmi_mesh_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept);
 
 /* screenWidth / screenHeight (src/Util.hs:186-188) as run-time values.  Allocates the
  * seven device planes the context owns (for the rows of its partition, see below) and
@@ -471,6 +500,8 @@ ptmi_ctx   *ptmi_group_member(ptmi_group *group, int i);        /* member i's co
 const char *ptmi_group_last_error(const ptmi_group *group);      /* per thread, as ptmi_last_error */
 int ptmi_group_set_scene(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes);
 int ptmi_group_set_scene_bvh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_bvh on every member */
+int ptmi_group_set_scene_mesh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
+                              const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_mesh on every member */
 int ptmi_group_resize(ptmi_group *group, int width, int height);
 int ptmi_group_init_output(ptmi_group *group, uint64_t seed0);
 int ptmi_group_reseed(ptmi_group *group, uint64_t seed0);
@@ -505,9 +536,9 @@ int ptmi_eval_distance_to_sphere(ptmi_ctx *ctx, const ptmi_sphere *spheres, cons
                                  int32_t *is_just, float *t, float *hit_normalp);
 int ptmi_eval_distance_to_plane(ptmi_ctx *ctx, const ptmi_plane *planes, const float *rays, int n,
                                 int32_t *is_just, float *t, float *hit_normalp);
-/* checkHit (src/Scene/Trace.hs:443-447) on the DEVICE against the context's current scene, linear or BVH, for n host rays
+/* checkHit (src/Scene/Trace.hs:443-447) on the DEVICE against the context's current scene, linear, BVH or mesh, for n host rays
  * (n x 6 floats: origin, direction): just_out[i] = 1 if ray i hits, then t_out[i] = its distance and idx_out[i] = the primitive
- * (spheres 0 .. n_spheres - 1, then planes); for a miss t_out[i] = 0 and idx_out[i] = -1.  The same selection the render kernels make. */
+ * (spheres 0 .. n_spheres - 1, then planes, then triangles); for a miss t_out[i] = 0 and idx_out[i] = -1.  The same selection the render kernels make. */
 int ptmi_eval_check_hit(ptmi_ctx *ctx, const float *rays, int n, float *t_out, int32_t *idx_out, int32_t *just_out);
 /* sin/cos of the device math used by anglesToQuaternion, for pinning against libm. */
 int ptmi_eval_sincos(ptmi_ctx *ctx, const float *x, int n, float *sin_out, float *cos_out);
