@@ -54,6 +54,10 @@ SYMBOLS = {
     "ptmi_bvh_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_mesh_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "ptmi_update_mesh_vertices": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_update_mesh_vertices_device": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_mesh_refit_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_mesh_read_layout": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "ptmi_local_rows": (C.c_int, [_vp]),
@@ -92,6 +96,7 @@ SYMBOLS = {
     "ptmi_group_set_scene": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
+    "ptmi_group_update_mesh_vertices": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_group_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_group_init_output": (C.c_int, [_vp, C.c_uint64]),
     "ptmi_group_reseed": (C.c_int, [_vp, C.c_uint64]),
@@ -205,6 +210,33 @@ def mesh_layout(triangles):
     return nodes[:got].copy(), order[:kept.value].copy()
 
 
+def mesh_refit_layout(triangles, nodes, order):
+    """ptmi_mesh_refit_layout: `nodes` and `order` of mesh_layout for the scene as set, refitted to the moved `triangles` (host code, no
+    device) -> the nodes with new boxes (a copy; ref and order are kept)."""
+    t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    out = np.array(nodes, dtype=BVH_NODE_DTYPE, copy=True).reshape(-1)
+    o = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+    rc = load_library().ptmi_mesh_refit_layout(_ptr(t) if t.size else None, t.size, _ptr(out), out.size, _ptr(o) if o.size else None, o.size)
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_mesh_refit_layout")
+    return out
+
+
+def _vertex_array(v):
+    """(n, 3, 3) or (n, 9) float32 vertices, v0 v1 v2 per triangle -> a contiguous array and n"""
+    a = np.ascontiguousarray(v, dtype=np.float32)
+    if a.ndim < 2 or a.size != a.shape[0] * 9:
+        raise ValueError("vertices must have shape (n, 3, 3) or (n, 9), not %r" % (a.shape,))
+    return a, a.shape[0]
+
+
+def _device_vertices(v):
+    """a contiguous float32 device tensor of n * 9 elements (anything with is_cuda and data_ptr()) -> (pointer, n)"""
+    if not v.is_cuda or not v.is_contiguous() or "float32" not in str(v.dtype) or v.numel() % 9:
+        raise ValueError("device vertices must be a contiguous float32 tensor of shape (n, 3, 3) or (n, 9) on the context's device")
+    return _vp(v.data_ptr()), v.numel() // 9
+
+
 def _mesh_args(spheres, triangles, planes):
     s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
     t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
@@ -278,6 +310,30 @@ class Context:
         keep, args = _mesh_args(spheres, triangles, planes)
         self._check(self._lib.ptmi_set_scene_mesh(self._h, *args))
         del keep
+
+    def update_mesh_vertices(self, v):
+        """ptmi_update_mesh_vertices: move the mesh scene's vertices and refit its hierarchy on the device.  v: (n, 3, 3) or (n, 9)
+        float32, v0 v1 v2 per triangle in set_scene_mesh's index order -- a numpy array (host entry), or an object with is_cuda and
+        data_ptr() such as a contiguous float32 torch tensor on the context's device (device entry; the caller orders its writes
+        before the context's stream)."""
+        if hasattr(v, "is_cuda") and hasattr(v, "data_ptr"):
+            ptr, n = _device_vertices(v)
+            self._check(self._lib.ptmi_update_mesh_vertices_device(self._h, ptr, n))
+        else:
+            a, n = _vertex_array(v)
+            self._check(self._lib.ptmi_update_mesh_vertices(self._h, _ptr(a) if n else None, n))
+
+    def mesh_read_layout(self):
+        """ptmi_mesh_read_layout: the triangle hierarchy the device holds now -> (nodes, order), as mesh_layout returns them"""
+        kept = C.c_int(0)
+        n_nodes = self._lib.ptmi_mesh_read_layout(self._h, None, 0, None, C.byref(kept))      # (nothing copied: the sizes)
+        if n_nodes < 0:
+            self._check(n_nodes)
+        nodes, order = np.zeros(n_nodes, BVH_NODE_DTYPE), np.zeros(max(1, kept.value), np.int32)
+        got = self._lib.ptmi_mesh_read_layout(self._h, _ptr(nodes), nodes.size, _ptr(order), C.byref(kept))
+        if got < 0:
+            self._check(got)
+        return nodes[:got], order[:kept.value].copy()
 
     def set_partition(self, stripe_rows, n_parts, part):
         self._check(self._lib.ptmi_set_partition(self._h, stripe_rows, n_parts, part))
@@ -555,6 +611,11 @@ class Group:
         s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
         p = np.ascontiguousarray(planes, dtype=PLANE_DTYPE)
         self._check(self._lib.ptmi_group_set_scene_bvh(self._h, _ptr(s) if s.size else None, s.size, _ptr(p) if p.size else None, p.size))
+
+    def update_mesh_vertices(self, v):
+        """ptmi_group_update_mesh_vertices: Context.update_mesh_vertices (host memory) on every member"""
+        a, n = _vertex_array(v)
+        self._check(self._lib.ptmi_group_update_mesh_vertices(self._h, _ptr(a) if n else None, n))
 
     def set_scene_mesh(self, spheres, triangles, planes):
         keep, args = _mesh_args(spheres, triangles, planes)

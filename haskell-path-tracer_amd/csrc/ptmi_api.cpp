@@ -19,6 +19,7 @@
 
 #include "ptmi_bvh.h"
 #include "ptmi_mesh.h"
+#include "ptmi_mesh_box.h"
 #include "ptmi_kernels.h"
 #include "ptmi_stage.h"
 
@@ -62,6 +63,13 @@ struct ptmi_ctx {
     bool scene_mesh = false;
     DeviceBlock d_mesh;
     MeshView mesh{};
+    // ... and what moving its vertices needs (ptmi_update_mesh_vertices): a second block of d_mesh's layout that an update writes and then
+    // SWAPS with d_mesh (a failed update leaves the scene as it was); the refit's plan -- kRefitWords result words, the triangles' leaf
+    // positions, the nodes level by level (MeshRefitPlan) -- in d_refit; the staged vertices of the host-pointer entry
+    DeviceBlock d_mesh_shadow, d_refit, d_refit_staging;
+    size_t mesh_nodes_f4 = 0, mesh_geom_f4 = 0, mesh_index_f4 = 0;   // d_mesh: nodes | records in leaf order | indices | records by index
+    size_t refit_leaf_pos_at = 0, refit_levels_at = 0;               // d_refit: byte offsets
+    std::vector<int32_t> refit_level_first;
 
     DeviceBlock d_live;      // unsigned long long
     DeviceBlock d_work;      // unsigned int
@@ -158,7 +166,7 @@ struct ptmi_ctx {
     // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
     template <class F> void each_block(F &&f)
     {
-        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_mesh_shadow, &d_refit, &d_refit_staging, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
                                &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
                                &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
             f(*b);
@@ -259,6 +267,25 @@ void release(DeviceBlock &b)
 {
     if (b.p) (void)hipFree(b.p);
     b = DeviceBlock{};
+}
+
+// (with the mesh scene they belong to; the stream is drained)
+void release_mesh_refit(ptmi_ctx *c)
+{
+    release(c->d_mesh_shadow);
+    release(c->d_refit);
+    release(c->d_refit_staging);
+    c->refit_level_first.clear();
+}
+
+// c->mesh's pointers into d_mesh, whichever of the two blocks that is
+void point_mesh_view(ptmi_ctx *c)
+{
+    const float4 *tb = c->d_mesh.as<float4>();
+    c->mesh.nodes = tb;
+    c->mesh.geom = tb + c->mesh_nodes_f4;
+    c->mesh.index = reinterpret_cast<const int *>(tb + c->mesh_nodes_f4 + c->mesh_geom_f4);
+    c->mesh.by_index = tb + c->mesh_nodes_f4 + c->mesh_geom_f4 + c->mesh_index_f4;
 }
 
 // `b` holds at least `bytes` (its contents are not kept).  A block that is replaced goes only once the stream is drained; with none
@@ -1269,6 +1296,7 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_mesh);
+    release_mesh_refit(c);
     c->d_scene = fresh;
     c->scene_bvh = false; c->bvh = BvhView{};
     c->scene_mesh = false; c->mesh = MeshView{};
@@ -1326,6 +1354,7 @@ int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, c
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_mesh);
+    release_mesh_refit(c);
     c->d_scene = fresh;
     c->d_bvh = fresh_bvh;
     c->scene_bvh = true;
@@ -1406,23 +1435,41 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
         std::memcpy(&tri[tn_f4 + 3 * k], &mb.records[(size_t)mb.order[k] * 12], 12 * sizeof(float));
     if (kept > 0) std::memcpy(&tri[tn_f4 + tg_f4], mb.order.data(), kept * sizeof(int32_t));
     if (n_triangles > 0) std::memcpy(&tri[tn_f4 + tg_f4 + ti_f4], mb.records.data(), (size_t)n_triangles * 12 * sizeof(float));
+    // d_refit: what ptmi_update_mesh_vertices needs of this hierarchy (the result words, the leaf positions, the nodes by level)
+    MeshRefitPlan plan;
+    mesh_refit_plan(mb, n_triangles, plan);
+    const size_t leaf_pos_at = 256, levels_at = leaf_pos_at + (((size_t)n_triangles * sizeof(int32_t) + 255) / 256) * 256;
+    std::vector<char> refit(levels_at + plan.level_nodes.size() * sizeof(int32_t), 0);
+    if (n_triangles > 0) std::memcpy(&refit[leaf_pos_at], plan.leaf_pos.data(), (size_t)n_triangles * sizeof(int32_t));
+    std::memcpy(&refit[levels_at], plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    // all three blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
-    DeviceBlock fresh, fresh_bvh, fresh_mesh;
+    // all blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
+    DeviceBlock fresh, fresh_bvh, fresh_mesh, fresh_shadow, fresh_refit;
     PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
     hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
     if (e == hipSuccess) e = allocate(fresh_mesh, tri.size() * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_shadow, tri.size() * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_refit, refit.size());
     if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(fresh_mesh.p, tri.data(), fresh_mesh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier` and `tri` die at return
-    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); PTMI_HIP(c, e); }
+    // (the second block starts as a copy: an update rewrites every record and every box of it, the references and indices never move)
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_shadow.p, fresh_mesh.p, fresh_mesh.bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_refit.p, refit.data(), fresh_refit.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier`, `tri` and `refit` die at return
+    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); PTMI_HIP(c, e); }
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_mesh);
+    release_mesh_refit(c);
     c->d_scene = fresh;
     c->d_bvh = fresh_bvh;
     c->d_mesh = fresh_mesh;
+    c->d_mesh_shadow = fresh_shadow;
+    c->d_refit = fresh_refit;
+    c->mesh_nodes_f4 = tn_f4; c->mesh_geom_f4 = tg_f4; c->mesh_index_f4 = ti_f4;
+    c->refit_leaf_pos_at = leaf_pos_at; c->refit_levels_at = levels_at;
+    c->refit_level_first = std::move(plan.level_first);
     c->scene_bvh = false;
     c->scene_mesh = true;
     const float4 *base = c->d_bvh.as<float4>();
@@ -1431,13 +1478,9 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     c->bvh.geom = base + nodes_f4;
     c->bvh.index = reinterpret_cast<const int *>(base + nodes_f4 + geom_f4);
     for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
-    const float4 *tb = c->d_mesh.as<float4>();
     c->mesh = MeshView{};
     c->mesh.spheres = c->bvh;
-    c->mesh.nodes = tb;
-    c->mesh.geom = tb + tn_f4;
-    c->mesh.index = reinterpret_cast<const int *>(tb + tn_f4 + tg_f4);
-    c->mesh.by_index = tb + tn_f4 + tg_f4 + ti_f4;
+    point_mesh_view(c);
     c->mesh.n_triangles = n_triangles;
     c->mesh.n_kept = (int)kept;
     for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = mb.lo[a]; c->mesh.hi[a] = mb.hi[a]; }
@@ -1449,6 +1492,99 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     for (int k = 0; k < n_triangles; ++k) c->has_glass |= triangles[k].brdf_tag == PTMI_GLASS;
     return PTMI_OK;
 #endif
+}
+
+// Moving the vertices of the current mesh scene (see include/ptmi.h).  One validation path, on the device: the check kernel reads the new
+// vertices only; the host reads its verdict and the new box back with the call's ONE synchronisation; only then are the writing kernels
+// enqueued -- into the second mesh block, which becomes the scene's when all of them are out.  c->mu is held.
+static int update_mesh_locked(ptmi_ctx *c, const float *d_vertices, int n_triangles)
+{
+    const int n = n_triangles;
+    unsigned int *result = c->d_refit.as<unsigned int>();
+    const int32_t *leaf_pos = reinterpret_cast<const int32_t *>(c->d_refit.as<char>() + c->refit_leaf_pos_at);
+    const int32_t *level_nodes = reinterpret_cast<const int32_t *>(c->d_refit.as<char>() + c->refit_levels_at);
+    unsigned int got[kRefitWords];
+    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kRefitHi * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(result + kRefitHi, 0, (kRefitWords - kRefitHi) * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, launch_mesh_refit_check(d_vertices, n, leaf_pos, result, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    if (got[kRefitError] != 0xffffffffu) {
+        const std::string who = "triangle " + std::to_string(got[kRefitError] >> 2);
+        switch (got[kRefitError] & 3u) {
+        case kRefitBadVertex: return fail(c, PTMI_EINVAL, who + ": a vertex is not finite: a box cannot bound it");
+        case kRefitBadNormal: return fail(c, PTMI_EINVAL, who + ": its edges, normal or normal^2 are not finite");
+        default:
+            return fail(c, PTMI_EINVAL, who + " had zero area when the scene was set and is in no leaf: it cannot gain area, set the scene again (ptmi_set_scene_mesh)");
+        }
+    }
+    float4 *shadow = c->d_mesh_shadow.as<float4>();
+    float4 *geom = shadow + c->mesh_nodes_f4, *by_index = geom + c->mesh_geom_f4 + c->mesh_index_f4;
+    PTMI_HIP(c, launch_mesh_refit_records(d_vertices, n, leaf_pos, by_index, geom, c->stream));
+    for (size_t lv = 0; lv + 1 < c->refit_level_first.size(); ++lv)
+        PTMI_HIP(c, launch_mesh_refit_level(shadow, geom, level_nodes + c->refit_level_first[lv], c->refit_level_first[lv + 1] - c->refit_level_first[lv], c->stream));
+    std::swap(c->d_mesh, c->d_mesh_shadow);
+    point_mesh_view(c);
+    for (int a = 0; a < 3; ++a) {
+        c->mesh.lo[a] = c->mesh.n_kept > 0 ? ordered_value(got[kRefitLo + a]) : 0.0f;
+        c->mesh.hi[a] = c->mesh.n_kept > 0 ? ordered_value(got[kRefitHi + a]) : 0.0f;
+    }
+    ++c->scene_version;
+    return PTMI_OK;
+}
+
+static int update_mesh_refusal(ptmi_ctx *c, const float *vertices, int n_triangles)
+{
+    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh): there are no vertices to move");
+    if (n_triangles != c->mesh.n_triangles)
+        return fail(c, PTMI_EINVAL, "the scene has " + std::to_string(c->mesh.n_triangles) + " triangles, not " + std::to_string(n_triangles) +
+                                        ": an update moves vertices, it does not change the topology");
+    if (n_triangles > 0 && !vertices) return fail(c, PTMI_EINVAL, "bad vertex arguments");
+    return PTMI_OK;
+}
+
+int ptmi_update_mesh_vertices_device(ptmi_ctx *c, const float *d_vertices, int n_triangles)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = update_mesh_refusal(c, d_vertices, n_triangles)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    return update_mesh_locked(c, d_vertices, n_triangles);
+}
+
+int ptmi_update_mesh_vertices(ptmi_ctx *c, const float *vertices, int n_triangles)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = update_mesh_refusal(c, vertices, n_triangles)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    if (n_triangles > 0) {
+        const size_t bytes = (size_t)n_triangles * 9 * sizeof(float);
+        if (int rc = grow(c, c->d_refit_staging, bytes, "vertex staging")) return rc;
+        CopySpan span{c->d_refit_staging.p, const_cast<float *>(vertices), bytes};
+        PTMI_HIP(c, copy_to_device(c, &span, 1));
+    }
+    return update_mesh_locked(c, c->d_refit_staging.as<float>(), n_triangles);
+}
+
+int ptmi_mesh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh)");
+    const size_t n_nodes = c->mesh_nodes_f4 / 4, kept = (size_t)c->mesh.n_kept;
+    if (!nodes && !order) {                                  // the sizes only
+        if (n_kept) *n_kept = (int)kept;
+        return (int)n_nodes;
+    }
+    if (!nodes || (kept > 0 && !order)) return fail(c, PTMI_EINVAL, "bad layout arguments");
+    if (node_capacity < 0 || (size_t)node_capacity < n_nodes) return fail(c, PTMI_ELIMIT, "node_capacity is smaller than the hierarchy");
+    PTMI_HIP(c, hipSetDevice(c->device));
+    CopySpan spans[2] = {{const_cast<float4 *>(c->mesh.nodes), nodes, n_nodes * sizeof(ptmi_bvh_node)},
+                         {const_cast<int *>(c->mesh.index), order, kept * sizeof(int32_t)}};
+    PTMI_HIP(c, copy_to_host(c, spans, 2));
+    if (n_kept) *n_kept = (int)kept;
+    return (int)n_nodes;
 }
 
 int ptmi_set_partition(ptmi_ctx *c, int stripe_rows, int n_parts, int part)

@@ -260,6 +260,13 @@ hipError_t launch_render_inline_mesh(const RenderArgs &a, const MeshView &mesh, 
 hipError_t launch_render_streams_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
 hipError_t launch_render_streams_tree_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
 hipError_t launch_eval_check_hit_mesh(SceneView scene, const MeshView &mesh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
+// Moving a mesh scene's vertices (ptmi_update_mesh_vertices; ptmi_mesh_refit.hip).  vertices: 9 floats per triangle by original index, device
+// memory; leaf_pos: per triangle its position in the leaf order or -1; result: kRefitWords words (ptmi_mesh_box.h), all ones in
+// [0, kRefitHi), zero behind, at launch.  check writes `result` only; records writes both copies of the records; level the boxes of
+// `count` nodes whose children are complete (one launch per level of MeshRefitPlan, the deepest first).
+hipError_t launch_mesh_refit_check(const float *vertices, int n, const int32_t *leaf_pos, unsigned int *result, hipStream_t stream);
+hipError_t launch_mesh_refit_records(const float *vertices, int n, const int32_t *leaf_pos, float4 *by_index, float4 *geom, hipStream_t stream);
+hipError_t launch_mesh_refit_level(float4 *nodes, const float4 *geom, const int32_t *level_nodes, int count, hipStream_t stream);
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

@@ -9,6 +9,7 @@
 // triangle's box is its vertices' box padded by 2^-16 (max |coordinate| + extent) for the rounding of the hit point and the edge
 // functions (the derivation is at check_hit_mesh, ptmi_mesh_device.h).
 #include "ptmi_mesh.h"
+#include "ptmi_mesh_box.h"
 
 #include <algorithm>
 #include <cmath>
@@ -20,15 +21,7 @@ namespace ptmi {
 
 namespace {
 
-constexpr double kPadFactor = 1.0 / 65536.0;
 constexpr int kLeafCap = 255;                    // what a leaf reference can encode
-
-float round_up(double v)
-{
-    float f = (float)v;
-    if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-    return f;
-}
 
 struct Builder {
     const ptmi_triangle *tri;
@@ -37,27 +30,15 @@ struct Builder {
     std::vector<int32_t> idx;
     std::vector<ptmi_bvh_node> nodes;
 
-    static void store(ptmi_bvh_node &nd, int c, const double l[3], const double h[3])
-    {
-        for (int a = 0; a < 3; ++a) {
-            const float cf = (float)(0.5 * (l[a] + h[a]));
-            nd.center[c][a] = cf;
-            nd.half[c][a] = round_up(std::max(h[a] - (double)cf, (double)cf - l[a]));
-        }
-    }
+    static void store(ptmi_bvh_node &nd, int c, const double l[3], const double h[3]) { box_store(nd.center[c], nd.half[c], l, h); }
 
     void set_box_of_node(ptmi_bvh_node &nd, int c, int inner) const
     {
         const ptmi_bvh_node &in = nodes[(size_t)inner];
         double l[3], h[3];
-        for (int a = 0; a < 3; ++a) { l[a] = std::numeric_limits<double>::infinity(); h[a] = -l[a]; }
-        for (int k = 0; k < 2; ++k) {
-            if (in.ref[k] == -1) continue;
-            for (int a = 0; a < 3; ++a) {
-                l[a] = std::min(l[a], (double)in.center[k][a] - (double)in.half[k][a]);
-                h[a] = std::max(h[a], (double)in.center[k][a] + (double)in.half[k][a]);
-            }
-        }
+        box_empty(l, h);
+        for (int k = 0; k < 2; ++k)
+            if (in.ref[k] != -1) box_join_stored(l, h, in.center[k], in.half[k]);
         store(nd, c, l, h);
         nd.inv_2r[c] = 0.0f;
     }
@@ -70,12 +51,8 @@ struct Builder {
             return;
         }
         double l[3], h[3];
-        for (int a = 0; a < 3; ++a) { l[a] = std::numeric_limits<double>::infinity(); h[a] = -l[a]; }
-        for (int k = b; k < e; ++k)
-            for (int a = 0; a < 3; ++a) {
-                l[a] = std::min(l[a], lo[3 * (size_t)idx[k] + a]);
-                h[a] = std::max(h[a], hi[3 * (size_t)idx[k] + a]);
-            }
+        box_empty(l, h);
+        for (int k = b; k < e; ++k) box_join(l, h, &lo[3 * (size_t)idx[k]], &hi[3 * (size_t)idx[k]]);
         store(nd, c, l, h);
     }
 
@@ -147,13 +124,11 @@ int mesh_build(const ptmi_triangle *tris, int n, MeshBuild &out, std::string *wh
             return refuse(PTMI_EINVAL, "a triangle's vertex is not finite: a box cannot bound it");
         if (!finite3(t.color) || !std::isfinite(t.illuminance) || !std::isfinite(t.brdf_param))
             return refuse(PTMI_EINVAL, "a triangle's colour, illuminance or brdf_param is not finite");
-        // the derived normal, by the device's operations (ptmi_mesh_device.h): e1 = v1 - v0, e2 = v2 - v0, n = cross(e1, e2)
-        const float e1[3] = {t.v1[0] - t.v0[0], t.v1[1] - t.v0[1], t.v1[2] - t.v0[2]};
-        const float e2[3] = {t.v2[0] - t.v0[0], t.v2[1] - t.v0[1], t.v2[2] - t.v0[2]};
-        const float nv[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        const float nn = (nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2];
-        if (!finite3(e1) || !finite3(e2) || !finite3(nv) || !std::isfinite(nn))
-            return refuse(PTMI_EINVAL, "a triangle's edges, normal or normal^2 are not finite");
+        // the derived normal, by the device's operations (ptmi_mesh_box.h): e1 = v1 - v0, e2 = v2 - v0, n = cross(e1, e2)
+        const TriangleNormal tn = triangle_normal(t.v0, t.v1, t.v2);
+        const float *nv = tn.n;
+        const float nn = tn.nn;
+        if (!tn.finite) return refuse(PTMI_EINVAL, "a triangle's edges, normal or normal^2 are not finite");
         float *r = &out.records[(size_t)i * 12];
         const float *v[3] = {t.v0, t.v1, t.v2};
         for (int k = 0; k < 3; ++k) { r[4 * k] = v[k][0]; r[4 * k + 1] = v[k][1]; r[4 * k + 2] = v[k][2]; }
@@ -163,21 +138,8 @@ int mesh_build(const ptmi_triangle *tris, int n, MeshBuild &out, std::string *wh
         }
         const float len = std::sqrt(nn);
         r[3] = nv[0] / len; r[7] = nv[1] / len; r[11] = nv[2] / len;
-        double m = 0.0, ext = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const double l = std::min({(double)t.v0[a], (double)t.v1[a], (double)t.v2[a]});
-            const double h = std::max({(double)t.v0[a], (double)t.v1[a], (double)t.v2[a]});
-            m = std::max({m, std::fabs(l), std::fabs(h)});
-            ext = std::max(ext, h - l);
-        }
-        const double pad = kPadFactor * (m + ext);
-        for (int a = 0; a < 3; ++a) {
-            const double l = std::min({(double)t.v0[a], (double)t.v1[a], (double)t.v2[a]});
-            const double h = std::max({(double)t.v0[a], (double)t.v1[a], (double)t.v2[a]});
-            bd.lo[3 * (size_t)i + a] = l - pad;
-            bd.hi[3 * (size_t)i + a] = h + pad;
-            bd.centroid[3 * (size_t)i + a] = ((double)t.v0[a] + (double)t.v1[a] + (double)t.v2[a]) / 3.0;
-        }
+        triangle_box(t.v0, t.v1, t.v2, &bd.lo[3 * (size_t)i], &bd.hi[3 * (size_t)i]);
+        for (int a = 0; a < 3; ++a) bd.centroid[3 * (size_t)i + a] = ((double)t.v0[a] + (double)t.v1[a] + (double)t.v2[a]) / 3.0;
         bd.idx.push_back(i);
     }
     const int kept = (int)bd.idx.size();
@@ -198,7 +160,92 @@ int mesh_build(const ptmi_triangle *tris, int n, MeshBuild &out, std::string *wh
     return PTMI_OK;
 }
 
+void mesh_refit_plan(const MeshBuild &built, int n_triangles, MeshRefitPlan &out)
+{
+    out.leaf_pos.assign((size_t)n_triangles, -1);
+    for (size_t k = 0; k < built.order.size(); ++k) out.leaf_pos[(size_t)built.order[k]] = (int32_t)k;
+    // children have larger ids than their parent (child() appends before it fills): one ascending pass gives every level
+    const size_t n = built.nodes.size();
+    std::vector<int32_t> level(n, 0);
+    int deepest = 0;
+    for (size_t id = 0; id < n; ++id)
+        for (int c = 0; c < 2; ++c)
+            if (built.nodes[id].ref[c] >= 0) {
+                level[(size_t)built.nodes[id].ref[c]] = level[id] + 1;
+                deepest = std::max(deepest, level[id] + 1);
+            }
+    std::vector<int32_t> count((size_t)deepest + 2, 0);
+    for (size_t id = 0; id < n; ++id) ++count[(size_t)(deepest - level[id]) + 1];
+    for (size_t k = 1; k < count.size(); ++k) count[k] += count[k - 1];
+    out.level_first = count;
+    out.level_nodes.assign(n, 0);
+    for (size_t id = 0; id < n; ++id) out.level_nodes[(size_t)count[(size_t)(deepest - level[id])]++] = (int32_t)id;
+}
+
+int mesh_refit(const ptmi_triangle *tris, int n, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept, std::string *why)
+{
+    auto refuse = [&](const std::string &msg) { if (why) *why = msg; return (int)PTMI_EINVAL; };
+    if (n < 0 || n_nodes < 1 || n_kept < 0 || n_kept > n || !nodes || (n > 0 && !tris) || (n_kept > 0 && !order)) return refuse("bad refit arguments");
+    // the topology must be one ptmi_mesh_layout can have made: every node but the root referred to once, by a node before it; the
+    // leaves a partition of the leaf order; the leaf order distinct triangles
+    long long inner = 0, in_leaves = 0;
+    for (int id = 0; id < n_nodes; ++id)
+        for (int c = 0; c < 2; ++c) {
+            const int32_t ref = nodes[id].ref[c];
+            if (ref >= 0) {
+                if (ref <= id || ref >= n_nodes) return refuse("the nodes are not a hierarchy of ptmi_mesh_layout (a child reference out of range: wrong n_nodes?)");
+                ++inner;
+            } else if (ref != -1) {
+                const uint32_t v = (uint32_t)(-1 - ref);
+                if ((long long)(v >> 8) + (v & 255u) > n_kept) return refuse("a leaf lies beyond the leaf order (wrong n_kept?)");
+                in_leaves += v & 255u;
+            }
+        }
+    if (inner != n_nodes - 1 || in_leaves != n_kept) return refuse("the nodes and the leaf order do not belong together (wrong n_nodes or n_kept?)");
+    std::vector<char> in_leaf((size_t)n, 0);
+    for (int k = 0; k < n_kept; ++k) {
+        if (order[k] < 0 || order[k] >= n || in_leaf[(size_t)order[k]]) return refuse("the leaf order does not name distinct triangles");
+        in_leaf[(size_t)order[k]] = 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        const TriangleNormal tn = triangle_normal(tris[i].v0, tris[i].v1, tris[i].v2);
+        if (!tn.vertices_finite) return refuse("triangle " + std::to_string(i) + ": a vertex is not finite: a box cannot bound it");
+        if (!tn.finite) return refuse("triangle " + std::to_string(i) + ": its edges, normal or normal^2 are not finite");
+        if (!in_leaf[(size_t)i] && tn.nn > 0.0f)
+            return refuse("triangle " + std::to_string(i) + " had zero area when the scene was set and is in no leaf: it cannot gain area, set the scene again (ptmi_set_scene_mesh)");
+    }
+    for (int id = n_nodes - 1; id >= 0; --id) {
+        ptmi_bvh_node &nd = nodes[id];
+        for (int c = 0; c < 2; ++c) {
+            const int32_t ref = nd.ref[c];
+            if (ref == -1) continue;
+            double l[3], h[3];
+            box_empty(l, h);
+            if (ref >= 0) {
+                const ptmi_bvh_node &in = nodes[ref];
+                for (int k = 0; k < 2; ++k)
+                    if (in.ref[k] != -1) box_join_stored(l, h, in.center[k], in.half[k]);
+            } else {
+                const uint32_t v = (uint32_t)(-1 - ref);
+                for (uint32_t k = v >> 8; k < (v >> 8) + (v & 255u); ++k) {
+                    const ptmi_triangle &t = tris[order[k]];
+                    double tl[3], th[3];
+                    triangle_box(t.v0, t.v1, t.v2, tl, th);
+                    box_join(l, h, tl, th);
+                }
+            }
+            box_store(nd.center[c], nd.half[c], l, h);
+        }
+    }
+    return PTMI_OK;
+}
+
 }  // namespace ptmi
+
+extern "C" int ptmi_mesh_refit_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept)
+{
+    return ptmi::mesh_refit(triangles, n_triangles, nodes, n_nodes, order, n_kept, nullptr);
+}
 
 extern "C" int ptmi_mesh_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept)
 {

@@ -20,4 +20,16 @@ struct MeshBuild {
 // PTMI_OK, PTMI_ELIMIT (too many triangles) or PTMI_EINVAL (non-finite vertex or material data); `why` says which.
 int mesh_build(const ptmi_triangle *triangles, int n_triangles, MeshBuild &out, std::string *why);
 
+// What the device refit (ptmi_update_mesh_vertices, ptmi_mesh_refit.hip) needs of a built hierarchy besides the hierarchy itself.
+struct MeshRefitPlan {
+    std::vector<int32_t> leaf_pos;      // per original triangle: its position in the leaf order, -1 when it is in no leaf (zero area)
+    std::vector<int32_t> level_nodes;   // every node, the deepest level first: children always come before their parent
+    std::vector<int32_t> level_first;   // launches + 1 offsets into level_nodes, one launch per level
+};
+void mesh_refit_plan(const MeshBuild &built, int n_triangles, MeshRefitPlan &out);
+
+// ptmi_mesh_refit_layout: the boxes of `nodes` recomputed for the moved `triangles`, topology (`ref`, `order`) kept.
+// PTMI_OK or PTMI_EINVAL; `why` says which triangle or which part of the topology.
+int mesh_refit(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept, std::string *why);
+
 }  // namespace ptmi

@@ -197,6 +197,13 @@ public:
         } else if (kind == SceneKind::Bvh) check(ptmi_set_scene_bvh(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
         else check(ptmi_set_scene(ctx_.get(), sp.data(), (int)sp.size(), pl.data(), (int)pl.size()));
     }
+    // Move the vertices of a SceneKind::Mesh scene (ptmi_update_mesh_vertices): 9 floats per triangle, v0 v1 v2, in the order of
+    // SceneDescription::triangles.  The hierarchy is refitted on the device; materials, spheres and planes stay.
+    void update_mesh_vertices(const std::vector<float> &vertices)
+    {
+        if (vertices.size() % 9) throw PtmiError(PTMI_EINVAL, "update_mesh_vertices takes 9 floats per triangle");
+        check(ptmi_update_mesh_vertices(ctx_.get(), vertices.data(), (int)(vertices.size() / 9)));
+    }
     ptmi_ctx *get() const { return ctx_.get(); }
     const std::shared_ptr<ptmi_ctx> &shared() const { return ctx_; }
     static std::string buildId() { return ptmi_build_id(); }      // what the loaded libptmi was built from: print it next to any timing

@@ -163,6 +163,43 @@ def triangles_of(vertices, faces, material):
     return t
 
 
+def triangle_vertices(triangles):
+    """The vertices of TRIANGLE_DTYPE records as Context.update_mesh_vertices takes them -> (n, 3, 3) float32, [k] = (v0, v1, v2)"""
+    t = np.asarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    return np.ascontiguousarray(np.stack([t["v0"], t["v1"], t["v2"]], axis=1), dtype=np.float32)
+
+
+def with_vertices(triangles, v):
+    """A copy of the triangles with the vertices v ((n, 3, 3) or (n, 9), as triangle_vertices gives them); materials kept"""
+    t = np.array(triangles, dtype=TRIANGLE_DTYPE, copy=True).reshape(-1)
+    v = np.asarray(v, np.float32).reshape(len(t), 3, 3)
+    t["v0"], t["v1"], t["v2"] = v[:, 0], v[:, 1], v[:, 2]
+    return t
+
+
+def displaced(v, amount, kind="wave", centre=(1.0, 3.0, -16.0), radius=3.0, seed=0):
+    """Vertices (as triangle_vertices gives them) with those of mesh_room's icosphere -- everything within 1.5 radii of its centre --
+    moved along their own direction from the centre by up to amount * radius: kind "wave" a smooth wave over the sphere, kind "noise" a
+    value per vertex.  The displacement is a function of the vertex's POSITION (and the seed), so a vertex shared by several
+    triangles, or by a duplicate of a triangle, stays shared.  -> float32, the shape of v; tests and tools/mesh_refit_bench.py"""
+    a = np.asarray(v, np.float32)
+    p = a.reshape(-1, 3).astype(np.float64)
+    rel = p - np.asarray(centre, np.float64)
+    dist = np.linalg.norm(rel, axis=1)
+    inside = (dist < 1.5 * radius) & (dist > 0)
+    unit = rel / np.where(dist > 0, dist, 1.0)[:, None]
+    if kind == "wave":
+        f = np.sin(5.0 * unit[:, 0] + 0.7 * seed) * np.cos(4.0 * unit[:, 1]) + 0.5 * np.sin(7.0 * unit[:, 2] + 1.3 * seed)
+        f = f / 1.5
+    elif kind == "noise":
+        h = np.sin(p @ np.array([12.9898, 78.233, 37.719]) + 0.61 * seed) * 43758.5453
+        f = 2.0 * (h - np.floor(h)) - 1.0
+    else:
+        raise ValueError("kind is 'wave' or 'noise'")
+    out = np.where(inside[:, None], p + unit * (amount * radius * f)[:, None], p)
+    return np.ascontiguousarray(out.astype(np.float32).reshape(a.shape))
+
+
 def load_obj(path_or_text, material):
     """A minimal Wavefront OBJ reader: `v x y z` and `f a b c ...` lines only (1-based indices, negative ones counted back from the
     last vertex read, `a/b/c` forms use the position index); polygons are fan-triangulated (a b c, a c d, ...); every other line is

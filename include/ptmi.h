@@ -42,7 +42,9 @@ extern "C" {
                             * no option is read from the environment any more.  (0.4.0: options 8-12, ptmi_stream_schedule.)
                             * Added without a version bump: the bounding-volume-hierarchy scene (ptmi_set_scene_bvh, ptmi_group_set_scene_bvh,
                             * ptmi_bvh_layout, ptmi_bvh_node, PTMI_MAX_BVH_*) and ptmi_eval_check_hit; the mesh scene (ptmi_set_scene_mesh,
-                            * ptmi_group_set_scene_mesh, ptmi_mesh_layout, ptmi_triangle, PTMI_MAX_MESH_TRIANGLES). */
+                            * ptmi_group_set_scene_mesh, ptmi_mesh_layout, ptmi_triangle, PTMI_MAX_MESH_TRIANGLES); moving a mesh scene's
+                            * vertices (ptmi_update_mesh_vertices, ptmi_update_mesh_vertices_device, ptmi_group_update_mesh_vertices,
+                            * ptmi_mesh_refit_layout, ptmi_mesh_read_layout). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -202,6 +204,48 @@ int ptmi_set_scene_mesh(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres
  * Triangles of zero area are in no leaf: the return value's order has n_kept entries (*n_kept, may be NULL).  `nodes` needs
  * max(1, n_triangles) entries, `order` n_triangles.  Returns the number of nodes, or PTMI_ELIMIT / PTMI_EINVAL as ptmi_bvh_layout. */
 int ptmi_mesh_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept);
+
+/* Move the vertices of the current MESH scene without building anything on the host: the triangle hierarchy keeps its topology (child
+ * references, leaf order) and is REFIT on the device -- new boxes, bottom-up, one launch per level -- and both copies of the triangle
+ * records are rewritten.  `vertices` holds 9 floats per triangle, v0 v1 v2, in the index order of the `triangles` given to
+ * ptmi_set_scene_mesh, in host memory (ptmi_update_mesh_vertices: staged to the device, then the same path) or in device memory of the
+ * context's device (ptmi_update_mesh_vertices_device; read on the context's stream).  Materials, spheres and planes stay as set.
+ *   - Renders equal a fresh scene: after an update every render (all seven planes) and ptmi_eval_check_hit equal, bit for bit, those of
+ *     a context given ptmi_set_scene_mesh with the moved triangles: the device derives each record (v0, nx) (v1, ny) (v2, nz) by
+ *     ptmi_set_scene_mesh's own operations (edges, cross product in linear's component order, (nx^2 + ny^2) + nz^2, IEEE square root,
+ *     three IEEE divisions, each f32 operation rounded on its own), and check_hit returns the fold over spheres ++ planes ++ triangles
+ *     whatever hierarchy bounds the triangles.  The refitted boxes are those of ptmi_mesh_refit_layout, bit for bit.
+ *   - A failed update leaves the scene as it was: PTMI_ESTATE when the current scene is not a mesh scene; PTMI_EINVAL for a NULL
+ *     pointer, for an n_triangles other than the scene's, for a non-finite vertex, edge, normal or normal^2 (ptmi_set_scene_mesh's
+ *     conditions), and when a triangle that had ZERO AREA WHEN THE SCENE WAS SET would gain area -- it is in no leaf, the topology
+ *     cannot serve it: the message names the triangle, set the scene again.  The new vertices are validated by a kernel that writes
+ *     nothing of the scene, and the update is written into a second copy of the scene's mesh block that replaces the first only when
+ *     every launch is out: after PTMI_EHIP too the scene is the one before the call.
+ *   - A triangle in a leaf that collapses to zero area is accepted: it stays in its leaf with a NaN normal (never hit), its vertices
+ *     still count for its box.
+ *   - One host synchronisation per call (the verdict and the new box of the leaf triangles' vertices are read back together); the
+ *     writing kernels then run on the context's stream like a render.  Neither the old nor the new vertices are needed on the host.
+ * The topology is the one built for the scene AS SET: after large deformations the refitted boxes overlap more than a fresh build's
+ * and renders get slower, never different (DESIGN.md 5.8 has the measurements); call ptmi_set_scene_mesh again then.  Moving
+ * spheres or planes, or changing materials, is a scene call. */
+int ptmi_update_mesh_vertices(ptmi_ctx *ctx, const float *vertices, int n_triangles);          /* host memory   */
+int ptmi_update_mesh_vertices_device(ptmi_ctx *ctx, const float *d_vertices, int n_triangles); /* device memory */
+
+/* The device refit's specification and CPU twin (pure host code): `nodes` (n_nodes of them) and `order` (n_kept entries) as
+ * ptmi_mesh_layout returned them for the scene as set, `triangles` the moved ones.  Overwrites center and half of every child in
+ * place with ptmi_mesh_layout's own arithmetic -- a leaf child's box is the union of its triangles' padded vertex boxes, an inner
+ * child's the union of that node's two stored boxes, one sweep from the last node to node 0 (children have larger ids than their
+ * parent) -- and leaves ref and inv_2r (0) alone.  It depends on the topology and the current vertices only: unchanged vertices
+ * give ptmi_mesh_layout's nodes back byte for byte, and so does moving away and back.  PTMI_EINVAL, with nothing written, for nodes
+ * and order that do not belong together (a wrong n_nodes or n_kept), non-finite vertex data, or a triangle in no leaf that has area. */
+int ptmi_mesh_refit_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept);
+
+/* The triangle hierarchy the context's mesh scene holds NOW, copied back from the device (test and diagnostic surface, like
+ * ptmi_bvh_layout / ptmi_eval_check_hit): after updates, ptmi_mesh_refit_layout's nodes bit for bit.  `nodes` needs the scene's node
+ * count (node_capacity; PTMI_ELIMIT when too small), `order` its kept triangles (*n_kept, may be NULL).  With `nodes` and `order` both
+ * NULL nothing is copied: the return value and *n_kept say what to allocate.  Returns the number of nodes; PTMI_ESTATE when the
+ * current scene is not a mesh scene.  Synchronises the context's stream. */
+int ptmi_mesh_read_layout(ptmi_ctx *ctx, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept);
 
 /* screenWidth / screenHeight (src/Util.hs:186-188) as run-time values.  Allocates the
  * seven device planes the context owns (for the rows of its partition, see below) and
@@ -502,6 +546,7 @@ int ptmi_group_set_scene(ptmi_group *group, const ptmi_sphere *spheres, int n_sp
 int ptmi_group_set_scene_bvh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_bvh on every member */
 int ptmi_group_set_scene_mesh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
                               const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_mesh on every member */
+int ptmi_group_update_mesh_vertices(ptmi_group *group, const float *vertices, int n_triangles);   /* ptmi_update_mesh_vertices on every member */
 int ptmi_group_resize(ptmi_group *group, int width, int height);
 int ptmi_group_init_output(ptmi_group *group, uint64_t seed0);
 int ptmi_group_reseed(ptmi_group *group, uint64_t seed0);
