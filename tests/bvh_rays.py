@@ -143,3 +143,48 @@ def linear_fold(lib, spheres, planes, rays):
     P = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     lib.lin_check_hit(P(s), len(s), P(p), len(p), P(np.ascontiguousarray(rays, np.float32)), n, P(t), P(idx), P(just))
     return t, idx, just
+
+
+# ---- Beyond the field: placements, radii of every size and the admission test's brackets (tests/test_mesh_exact.py, test_gpu_mesh_exact.py) ----
+SCALES = (2.0 ** -20, 2.0 ** -12, 1.0, 3.0, 2.0 ** 12, 2.0 ** 20)
+OFFSETS = ((0.0, 0.0, 0.0), (1e3, -2e3, 5e2), (3e5, 1e5, -7e5), (1e7, 1e7, 1e7))
+
+
+def transformed(scene, scale, offset):
+    """(spheres, planes) with every position x -> x * scale + offset (in float64, rounded once) and every radius scaled"""
+    s, p = (np.array(a, copy=True) for a in scene)
+    off = np.asarray(offset, np.float64)
+    s["position"] = (s["position"].astype(np.float64) * scale + off).astype(np.float32)
+    s["radius"] = (s["radius"].astype(np.float64) * scale).astype(np.float32)
+    if len(p):
+        p["position"] = (p["position"].astype(np.float64) * scale + off).astype(np.float32)
+    return s, p
+
+
+def multiscale_field(n_spheres=3000, seed=0):
+    """Radii 2^-20 .. 2^20 in one field, each centre 2 .. 2^7 radii from the origin; sphere_field's materials and planes"""
+    rng = np.random.default_rng(seed + 2000)
+    s, p = world.sphere_field(n_spheres, seed)
+    r = 2.0 ** rng.uniform(-20, 20, len(s))
+    s["radius"] = r
+    s["position"] = _unit(rng.normal(size=(len(s), 3))) * (r * 2.0 ** rng.uniform(1, 7, len(s)))[:, None]
+    return s, p
+
+
+def admission_rays(spheres, n_rays, seed=0):
+    """Rays at sphere centres and silhouettes that bracket what the hierarchy serves: |d|^2 - 1 just below, at and just above +-2^-12, and
+    origins that put the reach on both sides of 2^40; a third each, the last third from 0.1 .. 100 radii away with |d| = 1"""
+    rng = np.random.default_rng(seed + 2001)
+    s = np.asarray(spheres)
+    c, r = s["position"].astype(np.float64), np.abs(s["radius"].astype(np.float64))
+    i = rng.integers(0, len(s), n_rays)
+    u = _unit(rng.normal(size=(n_rays, 3))).astype(np.float64)
+    v = np.cross(u, rng.normal(size=(n_rays, 3)))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    x = c[i] + v * (r[i] * rng.choice([0.0, 0.5, 1.0, 1.0 + 1e-6, 1.0 - 1e-6], n_rays))[:, None]
+    fam = np.arange(n_rays) % 3
+    dist = np.maximum(r[i], 1e-3) * 10.0 ** rng.uniform(-1, 2, n_rays)
+    dist = np.where(fam == 1, 2.0 ** 40 * rng.choice([0.25, 0.98, 1.02, 4.0], n_rays), dist)
+    eta = 2.0 ** -12 * rng.choice([1 - 1e-3, 1 - 1e-6, 1.0, 1 + 1e-6, 1 + 1e-3], n_rays) * rng.choice([-1.0, 1.0], n_rays)
+    d = u * np.where(fam == 0, np.sqrt(1.0 + eta), 1.0)[:, None]
+    return np.ascontiguousarray(np.hstack([x - u * dist[:, None], d]).astype(np.float32))
