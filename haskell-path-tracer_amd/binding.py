@@ -58,6 +58,9 @@ SYMBOLS = {
     "ptmi_update_mesh_vertices_device": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_mesh_refit_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_mesh_read_layout": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "ptmi_set_mesh_triangles": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_set_mesh_triangles_device": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_mesh_layout_morton": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "ptmi_local_rows": (C.c_int, [_vp]),
@@ -97,6 +100,7 @@ SYMBOLS = {
     "ptmi_group_set_scene_bvh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_update_mesh_vertices": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_group_set_mesh_triangles": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_group_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_group_init_output": (C.c_int, [_vp, C.c_uint64]),
     "ptmi_group_reseed": (C.c_int, [_vp, C.c_uint64]),
@@ -210,6 +214,20 @@ def mesh_layout(triangles):
     return nodes[:got].copy(), order[:kept.value].copy()
 
 
+def mesh_layout_morton(triangles):
+    """ptmi_mesh_layout_morton: the triangle hierarchy ptmi_set_mesh_triangles builds on the device (host code, no device) -> (nodes, order)
+    as mesh_layout returns them."""
+    t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    nodes = np.zeros(max(1, t.size), BVH_NODE_DTYPE)
+    order = np.zeros(max(1, t.size), np.int32)
+    kept = C.c_int(0)
+    got = load_library().ptmi_mesh_layout_morton(_ptr(t) if t.size else None, t.size, _ptr(nodes), nodes.size, _ptr(order) if t.size else None,
+                                                 C.byref(kept))
+    if got < 0:
+        raise PtmiError(got, "ptmi_mesh_layout_morton")
+    return nodes[:got].copy(), order[:kept.value].copy()
+
+
 def mesh_refit_layout(triangles, nodes, order):
     """ptmi_mesh_refit_layout: `nodes` and `order` of mesh_layout for the scene as set, refitted to the moved `triangles` (host code, no
     device) -> the nodes with new boxes (a copy; ref and order are kept)."""
@@ -235,6 +253,14 @@ def _device_vertices(v):
     if not v.is_cuda or not v.is_contiguous() or "float32" not in str(v.dtype) or v.numel() % 9:
         raise ValueError("device vertices must be a contiguous float32 tensor of shape (n, 3, 3) or (n, 9) on the context's device")
     return _vp(v.data_ptr()), v.numel() // 9
+
+
+def _device_triangles(t):
+    """a contiguous float32 device tensor of shape [n, 15], brdf_tag as its int32 bit pattern (anything with is_cuda and data_ptr()) ->
+    (pointer, n)"""
+    if not t.is_cuda or not t.is_contiguous() or "float32" not in str(t.dtype) or t.numel() % 15:
+        raise ValueError("device triangles must be a contiguous float32 tensor of shape (n, 15) on the context's device")
+    return _vp(t.data_ptr()), t.numel() // 15
 
 
 def _mesh_args(spheres, triangles, planes):
@@ -322,6 +348,18 @@ class Context:
         else:
             a, n = _vertex_array(v)
             self._check(self._lib.ptmi_update_mesh_vertices(self._h, _ptr(a) if n else None, n))
+
+    def set_mesh_triangles(self, triangles):
+        """ptmi_set_mesh_triangles: replace the mesh scene's triangles (any count) and build their hierarchy on the device.  triangles:
+        what set_scene_mesh accepts (host entry), or an object with is_cuda and data_ptr() such as a contiguous float32 torch tensor of
+        shape [n, 15] on the context's device, brdf_tag as its int32 bit pattern (device entry; the caller orders its writes before the
+        context's stream)."""
+        if hasattr(triangles, "is_cuda") and hasattr(triangles, "data_ptr"):
+            ptr, n = _device_triangles(triangles)
+            self._check(self._lib.ptmi_set_mesh_triangles_device(self._h, ptr, n))
+        else:
+            t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+            self._check(self._lib.ptmi_set_mesh_triangles(self._h, _ptr(t) if t.size else None, t.size))
 
     def mesh_read_layout(self):
         """ptmi_mesh_read_layout: the triangle hierarchy the device holds now -> (nodes, order), as mesh_layout returns them"""
@@ -616,6 +654,11 @@ class Group:
         """ptmi_group_update_mesh_vertices: Context.update_mesh_vertices (host memory) on every member"""
         a, n = _vertex_array(v)
         self._check(self._lib.ptmi_group_update_mesh_vertices(self._h, _ptr(a) if n else None, n))
+
+    def set_mesh_triangles(self, triangles):
+        """ptmi_group_set_mesh_triangles: Context.set_mesh_triangles (host memory) on every member"""
+        t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+        self._check(self._lib.ptmi_group_set_mesh_triangles(self._h, _ptr(t) if t.size else None, t.size))
 
     def set_scene_mesh(self, spheres, triangles, planes):
         keep, args = _mesh_args(spheres, triangles, planes)

@@ -20,6 +20,7 @@
 #include "ptmi_bvh.h"
 #include "ptmi_mesh.h"
 #include "ptmi_mesh_box.h"
+#include "ptmi_mesh_morton.h"
 #include "ptmi_kernels.h"
 #include "ptmi_stage.h"
 
@@ -70,6 +71,7 @@ struct ptmi_ctx {
     size_t mesh_nodes_f4 = 0, mesh_geom_f4 = 0, mesh_index_f4 = 0;   // d_mesh: nodes | records in leaf order | indices | records by index
     size_t refit_leaf_pos_at = 0, refit_levels_at = 0;               // d_refit: byte offsets
     std::vector<int32_t> refit_level_first;
+    bool fixed_has_glass = false;                                    // GLASS among the mesh scene's spheres and planes (ptmi_set_mesh_triangles keeps them)
 
     DeviceBlock d_live;      // unsigned long long
     DeviceBlock d_work;      // unsigned int
@@ -1489,6 +1491,7 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     c->has_glass = false;
     for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
     for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    c->fixed_has_glass = c->has_glass;
     for (int k = 0; k < n_triangles; ++k) c->has_glass |= triangles[k].brdf_tag == PTMI_GLASS;
     return PTMI_OK;
 #endif
@@ -1565,6 +1568,127 @@ int ptmi_update_mesh_vertices(ptmi_ctx *c, const float *vertices, int n_triangle
         PTMI_HIP(c, copy_to_device(c, &span, 1));
     }
     return update_mesh_locked(c, c->d_refit_staging.as<float>(), n_triangles);
+}
+
+// New triangles for the current mesh scene (see include/ptmi.h).  The check kernel reads the new triangles only; the host reads its
+// verdict, the kept count, the box and the GLASS flag back together; then fresh blocks -- the scene block with the new material tail,
+// both mesh blocks, the refit's plan -- are filled on the stream and become the scene's when all of it is through: update_mesh_locked's
+// discipline with fresh allocations, the sizes change.  c->mu is held.
+static int set_mesh_triangles_locked(ptmi_ctx *c, const float *d_triangles, int n_triangles)
+{
+    const int n = n_triangles;
+    unsigned int *result = c->d_refit.as<unsigned int>();
+    unsigned int got[kBuildWords];
+    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kBuildHi * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(result + kBuildHi, 0, (kBuildWords - kBuildHi) * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, launch_mesh_build_check(d_triangles, n, result, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    if (got[kBuildError] != 0xffffffffu) {
+        const std::string who = "triangle " + std::to_string(got[kBuildError] >> 2);
+        switch (got[kBuildError] & 3u) {
+        case kBuildBadVertex: return fail(c, PTMI_EINVAL, who + ": a vertex is not finite: a box cannot bound it");
+        case kBuildBadMaterial: return fail(c, PTMI_EINVAL, who + ": its colour, illuminance or brdf_param is not finite");
+        case kBuildBadNormal: return fail(c, PTMI_EINVAL, who + ": its edges, normal or normal^2 are not finite");
+        default: return fail(c, PTMI_EINVAL, who + ": unknown brdf_tag");
+        }
+    }
+    if (got[kBuildKept] > (unsigned int)n) return fail(c, PTMI_EHIP, "the check kernel counted more kept triangles than there are");
+    const int kept = (int)got[kBuildKept];
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    if (kept > 0)
+        for (int a = 0; a < 3; ++a) { lo[a] = ordered_value(got[kBuildLo + a]); hi[a] = ordered_value(got[kBuildHi + a]); }
+    // the topology and its levels are functions of the kept count alone (ptmi_mesh_morton.h)
+    MeshBuild mb;
+    MeshRefitPlan plan;
+    morton_topology(kept, mb.nodes);
+    mesh_refit_plan(mb, 0, plan);
+    const size_t prefix_f4 = c->d_scene.bytes / sizeof(float4) - 2 * (size_t)c->mesh.n_triangles;      // spheres and planes, and their materials
+    const size_t tn_f4 = mb.nodes.size() * 4, tg_f4 = 3 * (size_t)kept, ti_f4 = ((size_t)kept + 3) / 4, tb_f4 = 3 * (size_t)n;
+    const size_t leaf_pos_at = 256, levels_at = leaf_pos_at + (((size_t)n * sizeof(int32_t) + 255) / 256) * 256;
+    DeviceBlock fresh, fresh_mesh, fresh_shadow, fresh_refit, sort;
+    auto undo = [&]() { release(fresh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); release(sort); };
+    hipError_t e = allocate(fresh, (prefix_f4 + 2 * (size_t)n) * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_mesh, (tn_f4 + tg_f4 + ti_f4 + tb_f4) * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_shadow, fresh_mesh.bytes);
+    if (e == hipSuccess) e = allocate(fresh_refit, levels_at + plan.level_nodes.size() * sizeof(int32_t));
+    if (e == hipSuccess && kept > 0) e = allocate(sort, mesh_build_sort_bytes(n));
+    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
+    float4 *nodes = fresh_mesh.as<float4>(), *geom = nodes + tn_f4, *by_index = geom + tg_f4 + ti_f4;
+    int32_t *order = reinterpret_cast<int32_t *>(geom + tg_f4);
+    int32_t *leaf_pos = reinterpret_cast<int32_t *>(fresh_refit.as<char>() + leaf_pos_at);
+    int32_t *level_nodes = reinterpret_cast<int32_t *>(fresh_refit.as<char>() + levels_at);
+    if (prefix_f4 > 0) e = hipMemcpyAsync(fresh.p, c->d_scene.p, prefix_f4 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) {
+        CopySpan spans[2] = {{nodes, mb.nodes.data(), mb.nodes.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
+        e = copy_to_device(c, spans, 2);
+    }
+    if (e == hipSuccess && n > 0) {
+        if (kept > 0) e = launch_mesh_build_order(d_triangles, n, kept, lo, hi, sort.p, leaf_pos, order, c->stream);
+        else e = hipMemsetAsync(leaf_pos, 0xff, (size_t)n * sizeof(int32_t), c->stream);                // no triangle is in a leaf
+    }
+    if (e == hipSuccess) e = launch_mesh_build_scatter(d_triangles, n, kept, leaf_pos, by_index, geom, fresh.as<float4>() + prefix_f4, c->stream);
+    for (size_t lv = 0; lv + 1 < plan.level_first.size() && e == hipSuccess; ++lv)
+        e = launch_mesh_refit_level(nodes, geom, level_nodes + plan.level_first[lv], plan.level_first[lv + 1] - plan.level_first[lv], c->stream);
+    // (the second block starts as a copy: an update rewrites every record and every box of it, the references and indices never move)
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_shadow.p, fresh_mesh.p, fresh_mesh.bytes, hipMemcpyDeviceToDevice, c->stream);
+    // the stream is drained before the old blocks and the sort's scratch go (grow()'s rule), and a launch that failed on the device is
+    // seen while the old scene still stands; `mb` and `plan` die at return
+    const hipError_t drained = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = drained;
+    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
+    release(sort);
+    release(c->d_scene);
+    release(c->d_mesh);
+    release(c->d_mesh_shadow);
+    release(c->d_refit);
+    c->d_scene = fresh;
+    c->d_mesh = fresh_mesh;
+    c->d_mesh_shadow = fresh_shadow;
+    c->d_refit = fresh_refit;
+    c->mesh_nodes_f4 = tn_f4; c->mesh_geom_f4 = tg_f4; c->mesh_index_f4 = ti_f4;
+    c->refit_leaf_pos_at = leaf_pos_at; c->refit_levels_at = levels_at;
+    c->refit_level_first = std::move(plan.level_first);
+    point_mesh_view(c);
+    c->mesh.n_triangles = n;
+    c->mesh.n_kept = kept;
+    for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = lo[a]; c->mesh.hi[a] = hi[a]; }
+    c->has_glass = c->fixed_has_glass || got[kBuildGlass] != 0;
+    ++c->scene_version;
+    return PTMI_OK;
+}
+
+static int set_mesh_triangles_refusal(ptmi_ctx *c, const void *triangles, int n_triangles)
+{
+    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh): there are no triangles to replace");
+    if (n_triangles < 0 || (n_triangles > 0 && !triangles)) return fail(c, PTMI_EINVAL, "bad triangle arguments");
+    if (n_triangles > PTMI_MAX_MESH_TRIANGLES) return fail(c, PTMI_ELIMIT, "more triangles than PTMI_MAX_MESH_TRIANGLES");
+    if (n_triangles == 0 && c->n_spheres + c->n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
+    return PTMI_OK;
+}
+
+int ptmi_set_mesh_triangles_device(ptmi_ctx *c, const ptmi_triangle *d_triangles, int n_triangles)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = set_mesh_triangles_refusal(c, d_triangles, n_triangles)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    return set_mesh_triangles_locked(c, reinterpret_cast<const float *>(d_triangles), n_triangles);
+}
+
+int ptmi_set_mesh_triangles(ptmi_ctx *c, const ptmi_triangle *triangles, int n_triangles)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = set_mesh_triangles_refusal(c, triangles, n_triangles)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    if (n_triangles > 0) {
+        const size_t bytes = (size_t)n_triangles * sizeof(ptmi_triangle);
+        if (int rc = grow(c, c->d_refit_staging, bytes, "triangle staging")) return rc;
+        CopySpan span{c->d_refit_staging.p, const_cast<ptmi_triangle *>(triangles), bytes};
+        PTMI_HIP(c, copy_to_device(c, &span, 1));
+    }
+    return set_mesh_triangles_locked(c, c->d_refit_staging.as<float>(), n_triangles);
 }
 
 int ptmi_mesh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept)

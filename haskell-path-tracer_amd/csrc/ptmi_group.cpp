@@ -230,6 +230,15 @@ int ptmi_group_update_mesh_vertices(ptmi_group *g, const float *vertices, int n_
     return PTMI_OK;
 }
 
+int ptmi_group_set_mesh_triangles(ptmi_group *g, const ptmi_triangle *triangles, int n_triangles)
+{
+    if (!g) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(g->mu);
+    for (size_t i = 0; i < g->members.size(); ++i)
+        if (int rc = ptmi_set_mesh_triangles(g->members[i], triangles, n_triangles)) return member_fail(g, (int)i, rc);
+    return PTMI_OK;
+}
+
 int ptmi_group_resize(ptmi_group *g, int width, int height)
 {
     if (!g) return PTMI_EINVAL;

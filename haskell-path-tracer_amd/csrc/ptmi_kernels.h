@@ -267,6 +267,16 @@ hipError_t launch_eval_check_hit_mesh(SceneView scene, const MeshView &mesh, con
 hipError_t launch_mesh_refit_check(const float *vertices, int n, const int32_t *leaf_pos, unsigned int *result, hipStream_t stream);
 hipError_t launch_mesh_refit_records(const float *vertices, int n, const int32_t *leaf_pos, float4 *by_index, float4 *geom, hipStream_t stream);
 hipError_t launch_mesh_refit_level(float4 *nodes, const float4 *geom, const int32_t *level_nodes, int count, hipStream_t stream);
+// New triangles for a mesh scene (ptmi_set_mesh_triangles; ptmi_mesh_build.hip).  triangles: n ptmi_triangle records (15 words each), device memory.  check
+// writes `result` only (kBuildWords words, ptmi_mesh_morton.h: all ones in [0, kBuildHi), zero behind, at launch).  order: keys, the radix
+// sort (scratch: mesh_build_sort_bytes(n) bytes, free once the launches are through), then leaf_pos (n) and order (n_kept) from the
+// sorted indices; lo / hi: the box check found.  scatter: the records by index and in leaf order, and 2 n material float4.
+hipError_t launch_mesh_build_check(const float *triangles, int n, unsigned int *result, hipStream_t stream);
+size_t mesh_build_sort_bytes(int n);
+hipError_t launch_mesh_build_order(const float *triangles, int n, int n_kept, const float lo[3], const float hi[3], void *scratch, int32_t *leaf_pos,
+                                   int32_t *order, hipStream_t stream);
+hipError_t launch_mesh_build_scatter(const float *triangles, int n, int n_kept, const int32_t *leaf_pos, float4 *by_index, float4 *geom, float4 *materials,
+                                     hipStream_t stream);
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

@@ -10,6 +10,7 @@
 // functions (the derivation is at check_hit_mesh, ptmi_mesh_device.h).
 #include "ptmi_mesh.h"
 #include "ptmi_mesh_box.h"
+#include "ptmi_mesh_morton.h"
 
 #include <algorithm>
 #include <cmath>
@@ -240,7 +241,61 @@ int mesh_refit(const ptmi_triangle *tris, int n, ptmi_bvh_node *nodes, int n_nod
     return PTMI_OK;
 }
 
+// ptmi_mesh_layout_morton / the specification of ptmi_set_mesh_triangles: mesh_build's refusals, records and box; the leaf order by
+// (Morton key, index) and the topology of the kept count (ptmi_mesh_morton.h); the boxes by the refit over that topology.
+int mesh_build_morton(const ptmi_triangle *tris, int n, MeshBuild &out, std::string *why)
+{
+    auto refuse = [&](int code, const std::string &msg) { if (why) *why = msg; return code; };
+    if (n < 0 || (n > 0 && !tris)) return refuse(PTMI_EINVAL, "bad triangle arguments");
+    if (n > PTMI_MAX_MESH_TRIANGLES) return refuse(PTMI_ELIMIT, "more triangles than PTMI_MAX_MESH_TRIANGLES");
+    out.records.assign((size_t)n * 12, 0.0f);
+    out.order.clear();
+    for (int a = 0; a < 3; ++a) { out.lo[a] = std::numeric_limits<float>::infinity(); out.hi[a] = -out.lo[a]; }
+    for (int i = 0; i < n; ++i) {
+        const ptmi_triangle &t = tris[i];
+        const std::string who = "triangle " + std::to_string(i);
+        if (!finite3(t.v0) || !finite3(t.v1) || !finite3(t.v2)) return refuse(PTMI_EINVAL, who + ": a vertex is not finite: a box cannot bound it");
+        if (!finite3(t.color) || !std::isfinite(t.illuminance) || !std::isfinite(t.brdf_param))
+            return refuse(PTMI_EINVAL, who + ": its colour, illuminance or brdf_param is not finite");
+        const TriangleNormal tn = triangle_normal(t.v0, t.v1, t.v2);
+        if (!tn.finite) return refuse(PTMI_EINVAL, who + ": its edges, normal or normal^2 are not finite");
+        float *r = &out.records[(size_t)i * 12];
+        const float *v[3] = {t.v0, t.v1, t.v2};
+        for (int k = 0; k < 3; ++k) { r[4 * k] = v[k][0]; r[4 * k + 1] = v[k][1]; r[4 * k + 2] = v[k][2]; }
+        if (!(tn.nn > 0.0f)) {
+            r[3] = r[7] = r[11] = std::numeric_limits<float>::quiet_NaN();
+            continue;
+        }
+        const float len = std::sqrt(tn.nn);
+        r[3] = tn.n[0] / len; r[7] = tn.n[1] / len; r[11] = tn.n[2] / len;
+        for (int k = 0; k < 3; ++k)
+            for (int a = 0; a < 3; ++a) { out.lo[a] = std::min(out.lo[a], v[k][a]); out.hi[a] = std::max(out.hi[a], v[k][a]); }
+        out.order.push_back(i);
+    }
+    if (out.order.empty())
+        for (int a = 0; a < 3; ++a) { out.lo[a] = 0.0f; out.hi[a] = 0.0f; }
+    std::vector<uint64_t> key((size_t)n, 0);
+    for (int i : out.order) key[(size_t)i] = morton_key(tris[i].v0, tris[i].v1, tris[i].v2, out.lo, out.hi);
+    const uint64_t *kp = key.data();
+    std::sort(out.order.begin(), out.order.end(), [kp](int32_t x, int32_t y) { return kp[x] < kp[y] || (kp[x] == kp[y] && x < y); });
+    morton_topology((int)out.order.size(), out.nodes);
+    return mesh_refit(tris, n, out.nodes.data(), (int)out.nodes.size(), out.order.data(), (int)out.order.size(), why);
+}
+
 }  // namespace ptmi
+
+extern "C" int ptmi_mesh_layout_morton(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept)
+{
+    if (n_triangles < 0 || !nodes || (n_triangles > 0 && (!triangles || !order))) return PTMI_EINVAL;
+    if (n_triangles > PTMI_MAX_MESH_TRIANGLES) return PTMI_ELIMIT;
+    ptmi::MeshBuild b;
+    if (int rc = ptmi::mesh_build_morton(triangles, n_triangles, b, nullptr)) return rc;
+    if ((size_t)node_capacity < b.nodes.size()) return PTMI_ELIMIT;
+    std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(ptmi_bvh_node));
+    if (!b.order.empty()) std::memcpy(order, b.order.data(), b.order.size() * sizeof(int32_t));
+    if (n_kept) *n_kept = (int)b.order.size();
+    return (int)b.nodes.size();
+}
 
 extern "C" int ptmi_mesh_refit_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept)
 {

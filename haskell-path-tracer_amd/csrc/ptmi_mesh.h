@@ -20,6 +20,10 @@ struct MeshBuild {
 // PTMI_OK, PTMI_ELIMIT (too many triangles) or PTMI_EINVAL (non-finite vertex or material data); `why` says which.
 int mesh_build(const ptmi_triangle *triangles, int n_triangles, MeshBuild &out, std::string *why);
 
+// The same for ptmi_mesh_layout_morton, the host twin of ptmi_set_mesh_triangles (ptmi_mesh_morton.h): leaf order by Morton key, the
+// topology a function of the kept count, mesh_refit's boxes.
+int mesh_build_morton(const ptmi_triangle *triangles, int n_triangles, MeshBuild &out, std::string *why);
+
 // What the device refit (ptmi_update_mesh_vertices, ptmi_mesh_refit.hip) needs of a built hierarchy besides the hierarchy itself.
 struct MeshRefitPlan {
     std::vector<int32_t> leaf_pos;      // per original triangle: its position in the leaf order, -1 when it is in no leaf (zero area)

@@ -44,7 +44,9 @@ extern "C" {
                             * ptmi_bvh_layout, ptmi_bvh_node, PTMI_MAX_BVH_*) and ptmi_eval_check_hit; the mesh scene (ptmi_set_scene_mesh,
                             * ptmi_group_set_scene_mesh, ptmi_mesh_layout, ptmi_triangle, PTMI_MAX_MESH_TRIANGLES); moving a mesh scene's
                             * vertices (ptmi_update_mesh_vertices, ptmi_update_mesh_vertices_device, ptmi_group_update_mesh_vertices,
-                            * ptmi_mesh_refit_layout, ptmi_mesh_read_layout). */
+                            * ptmi_mesh_refit_layout, ptmi_mesh_read_layout); new triangles for a mesh scene, built on the device
+                            * (ptmi_set_mesh_triangles, ptmi_set_mesh_triangles_device, ptmi_group_set_mesh_triangles,
+                            * ptmi_mesh_layout_morton). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -226,7 +228,8 @@ int ptmi_mesh_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_n
  *   - One host synchronisation per call (the verdict and the new box of the leaf triangles' vertices are read back together); the
  *     writing kernels then run on the context's stream like a render.  Neither the old nor the new vertices are needed on the host.
  * The topology is the one built for the scene AS SET: after large deformations the refitted boxes overlap more than a fresh build's
- * and renders get slower, never different (DESIGN.md 5.8 has the measurements); call ptmi_set_scene_mesh again then.  Moving
+ * and renders get slower, never different (DESIGN.md 5.8 has the measurements); call ptmi_set_scene_mesh again then, or
+ * ptmi_set_mesh_triangles[_device] when the triangles live on the device or their count or connectivity changes.  Moving
  * spheres or planes, or changing materials, is a scene call. */
 int ptmi_update_mesh_vertices(ptmi_ctx *ctx, const float *vertices, int n_triangles);          /* host memory   */
 int ptmi_update_mesh_vertices_device(ptmi_ctx *ctx, const float *d_vertices, int n_triangles); /* device memory */
@@ -239,6 +242,40 @@ int ptmi_update_mesh_vertices_device(ptmi_ctx *ctx, const float *d_vertices, int
  * give ptmi_mesh_layout's nodes back byte for byte, and so does moving away and back.  PTMI_EINVAL, with nothing written, for nodes
  * and order that do not belong together (a wrong n_nodes or n_kept), non-finite vertex data, or a triangle in no leaf that has area. */
 int ptmi_mesh_refit_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, int n_kept);
+
+/* Replace the TRIANGLES of the current MESH scene -- another count, another connectivity, a fresh mesh -- without building anything on
+ * the host: `triangles` holds n_triangles records (0 .. PTMI_MAX_MESH_TRIANGLES), geometry and materials, in host memory
+ * (ptmi_set_mesh_triangles: staged to the device, then the same path) or in device memory of the context's device
+ * (ptmi_set_mesh_triangles_device; read on the context's stream).  Spheres, their hierarchy and planes stay as set.
+ *   - The result is a fresh scene: every render (all seven planes, Inline and Streams, GLASS included), ptmi_eval_check_hit and a later
+ *     ptmi_update_mesh_vertices[_device] equal, bit for bit, those of a context given ptmi_set_scene_mesh(spheres, new triangles, planes).
+ *     Records and materials are derived on the device by ptmi_set_scene_mesh's own operations, and check_hit returns the fold over
+ *     spheres ++ planes ++ triangles whatever hierarchy bounds the triangles.
+ *   - The hierarchy is NOT ptmi_mesh_layout's: the leaf order ascends by (Morton key of the centroid within the box of the kept
+ *     triangles' vertices, index) -- a radix sort on the device -- and the topology is a function of the kept count alone (equal-count
+ *     splits, ptmi_mesh_layout's depth); the boxes are the refit's over it.  ptmi_mesh_layout_morton is its specification and host twin:
+ *     ptmi_mesh_read_layout afterwards returns exactly its nodes and order.
+ *   - Refusals leave the scene as it was: PTMI_ESTATE when the current scene is not a mesh scene; PTMI_ELIMIT beyond the limit;
+ *     PTMI_EINVAL for NULL with n > 0, a negative n, 0 triangles in a scene without spheres and planes, and for everything
+ *     ptmi_set_scene_mesh refuses in a triangle -- a non-finite vertex, colour, illuminance or brdf_param, non-finite edges, normal or
+ *     normal^2, an unknown brdf_tag: the message names the triangle.  The new data is validated by a kernel that writes nothing of the
+ *     scene; the new blocks are written aside and replace the old ones only when all of it is through: after PTMI_EHIP / PTMI_ENOMEM
+ *     too the scene is the one before the call.
+ *   - A triangle of zero area keeps its index and material, has a NaN normal and is in no leaf, as with ptmi_set_scene_mesh; a later
+ *     update that would give it area is refused.
+ *   - Two host synchronisations per call: one reads the verdict, the kept count, the box and whether any triangle is GLASS, together;
+ *     one drains the stream before the old blocks and the sort's scratch are freed.  Neither the old nor the new triangles are needed
+ *     on the host.
+ * The Morton order with equal-count splits is another tree than ptmi_mesh_layout's longest-axis median splits.  Measured (DESIGN.md 5.8,
+ * profiles/mesh_build_bench.json): the call takes 1.5 / 17 ms from device memory against ptmi_set_scene_mesh's 16 / 426 ms at 82k / 1.3M
+ * triangles; a 1080p render over this tree takes x 0.80 / 0.96 of the time over ptmi_mesh_layout's at 1.3k / 82k triangles and x 1.15 at
+ * 1.3M: ptmi_set_scene_mesh remains the call for a static mesh. */
+int ptmi_set_mesh_triangles(ptmi_ctx *ctx, const ptmi_triangle *triangles, int n_triangles);          /* host memory   */
+int ptmi_set_mesh_triangles_device(ptmi_ctx *ctx, const ptmi_triangle *d_triangles, int n_triangles); /* device memory */
+
+/* The hierarchy ptmi_set_mesh_triangles builds, without a device (pure host code, deterministic): ptmi_mesh_layout's signature, return
+ * values and refusals; ptmi_mesh_refit_layout accepts the result and leaves it byte-identical. */
+int ptmi_mesh_layout_morton(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept);
 
 /* The triangle hierarchy the context's mesh scene holds NOW, copied back from the device (test and diagnostic surface, like
  * ptmi_bvh_layout / ptmi_eval_check_hit): after updates, ptmi_mesh_refit_layout's nodes bit for bit.  `nodes` needs the scene's node
@@ -547,6 +584,7 @@ int ptmi_group_set_scene_bvh(ptmi_group *group, const ptmi_sphere *spheres, int 
 int ptmi_group_set_scene_mesh(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
                               const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_mesh on every member */
 int ptmi_group_update_mesh_vertices(ptmi_group *group, const float *vertices, int n_triangles);   /* ptmi_update_mesh_vertices on every member */
+int ptmi_group_set_mesh_triangles(ptmi_group *group, const ptmi_triangle *triangles, int n_triangles);   /* ptmi_set_mesh_triangles on every member */
 int ptmi_group_resize(ptmi_group *group, int width, int height);
 int ptmi_group_init_output(ptmi_group *group, uint64_t seed0);
 int ptmi_group_reseed(ptmi_group *group, uint64_t seed0);
