@@ -70,7 +70,17 @@ enum { PTMI_STREAMS = 0, PTMI_INLINE = 1 };
  * src/Scene/Trace.hs:62-67).  On one GPU a scene with GLASS is rendered by the per-pixel TREE WALK (deterministic, bit-exact
  * against the oracle: one adder per colour word); one PART of a partitioned image at >= 256 samples per call by the stream ("wavefront")
  * form -- BASELINE configs[4]'s path: faster where the job is bounded by its slowest part, colours through float atomics in no defined
- * order.  PTMI_OPT_STREAMS_FORM chooses explicitly.  See DESIGN.md 5.5. */
+ * order.  PTMI_OPT_STREAMS_FORM chooses explicitly.  See DESIGN.md 5.5.
+ * What a GLASS hit does, for a ray of direction d that meets the normal n at the point p with the generator state `seed`:
+ *   (rv, seed') = genVec seed                       -- drawn and discarded, as for every material (src/Scene/Trace.hs:402)
+ *   dn = d . n ; cosi = -dn ; eta = 1 / ior ; k = 1 - (eta*eta) * (1 - cosi*cosi)
+ *   reflection = d - (2*dn) *^ n                     -- the Glossy formula (src/Scene/Trace.hs:421-422)
+ *   r0 = ((1-ior)/(1+ior))^2 ; m = 1 - cosi ; R = r0 + (1-r0) * (((m*m)*(m*m))*m)   -- Schlick
+ *   k < 0 (total internal reflection):  R = 1, refraction = reflection
+ *   else refraction = eta *^ d + (eta*cosi - sqrt k) *^ n
+ *   child 0 = (p + reflection ^* epsilon, reflection), throughput * (color ^* R),     seed'
+ *   child 1 = (p + refraction ^* epsilon, refraction), throughput * (color ^* (1-R)), seed' advanced one more draw
+ * Back faces are culled by distanceTo, so a refracted ray never meets the far side of its own sphere. */
 enum { PTMI_MATTE = 0, PTMI_GLOSSY = 1, PTMI_GLASS = 2 };
 
 #define PTMI_MAX_PRIMITIVES 1024   /* spheres + planes staged in LDS per workgroup */

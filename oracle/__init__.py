@@ -49,6 +49,10 @@ class _Sfc(C.Structure):
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("c", C.c_uint32), ("counter", C.c_uint32)]
 
 
+class _Primary(C.Structure):
+    _fields_ = [("pos", _V3), ("center", _V3), ("right", _V3), ("top", _V3), ("inv_w_dummy", C.c_float)]
+
+
 class _Opts(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_int), ("streams_seed_rule", C.c_int), ("n_threads", C.c_int)]
 
@@ -110,6 +114,8 @@ def lib():
         L.ora_random_float.restype = C.c_float; L.ora_random_float.argtypes = [C.POINTER(_Sfc)]
         L.ora_sfc32_seed3.restype = _Sfc; L.ora_sfc32_seed3.argtypes = [C.c_uint32] * 3
         L.ora_max_threads.restype = C.c_int
+        L.ora_primary_setup.restype = _Primary; L.ora_primary_setup.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ora_primary_ray.restype = _Ray; L.ora_primary_ray.argtypes = [C.POINTER(_Primary), C.c_int64, C.c_int64, C.c_int, C.c_int]
         _lib = L
     return _lib
 
@@ -181,6 +187,14 @@ def _scene(spheres, planes):
 def check_hit(spheres, planes, origin, direction):
     sc, keep = _scene(spheres, planes)
     return _hit_tuple(lib().ora_check_hit(C.byref(sc), _ray(origin, direction)))
+
+
+def primary_ray(camera, width, height, x, y):
+    """-> (origin, direction) float32 of the primary ray of pixel (x, y)   (Trace.hs:205-262)"""
+    cam = np.ascontiguousarray(camera, CAMERA_DTYPE)
+    u = lib().ora_primary_setup(_p(cam), width, height)
+    r = lib().ora_primary_ray(C.byref(u), int(x), int(y), width, height)
+    return (np.array([r.origin.x, r.origin.y, r.origin.z], np.float32), np.array([r.direction.x, r.direction.y, r.direction.z], np.float32))
 
 
 def gen_seeds(seed0, first_index, n):

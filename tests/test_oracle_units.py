@@ -2,11 +2,16 @@
 render-level identities the reference's structure implies.  CPU only."""
 import ctypes
 import ctypes.util
+import os
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import assert_planes_equal, initial_planes
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_render  # noqa: E402
 
 F = np.float32
 
@@ -155,8 +160,17 @@ def test_camera_direction_is_unit_and_matches_float64(ora, pkg, angles):
     # probe the centre: width=height=1 -> x=0,y=0 -> screen (-1, +1).  Use check via oracle primary setup:
     sp1, pl1 = pkg.world.main_scene()
     cam = pkg.world.camera((0, 0, 0), angles, 90)
-    # centre direction = normalize(center - pos) is not exposed; check unit length of the rotated forward
     assert abs(np.linalg.norm(want) - 1.0) < 1e-12
+    # the oracle's primary directions at the corners, the centre and ragged pixels against exact_render.primary_rays, within its derived bound
+    for fov, (w, h) in ((90, (64, 48)), (60, (37, 23))):
+        cam = pkg.world.camera((1.0, -1.6, -4.8), angles, fov)
+        pos, d64, bound = exact_render.primary_rays(cam, w, h)
+        for x, y in ((0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, h // 2), (5, 17), (w - 3, 2)):
+            o, d = ora.primary_ray(cam, w, h, x, y)
+            assert np.array_equal(o.astype(np.float64), pos)
+            err = np.linalg.norm(d.astype(np.float64) - d64[y * w + x])
+            assert err <= exact_render.SAFETY * bound[y * w + x], (fov, x, y, err, bound[y * w + x])
+    cam = pkg.world.camera((0, 0, 0), angles, 90)
     out, _ = ora.render_inline(sp1, pl1, cam, 2, 2, 1, 1, initial_planes(ora, 2, 2))
     assert all(np.all(np.isfinite(p)) for p in out[:3])
 
