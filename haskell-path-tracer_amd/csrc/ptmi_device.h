@@ -117,6 +117,56 @@ __device__ __noinline__ HitSel check_hit_exact(ScenePtr S, int ns, int np, V3 o,
     /* Nothing iff tca < 0 || d2 > rad**2 || t < 0;  d2 > r2 <=> r2 - d2 < 0 (exact: gradual underflow) */                         \
     const bool cand = !(tca < 0.0f) && !(x < 0.0f)
 
+// distanceTo @Plane (Intersection.hs:57-62) folded into the accumulator after the spheres, for check_hit and the hierarchies' walks
+// (ptmi_bvh_device.h, ptmi_mesh_device.h): ONE text, so that all of them make the same operations.  at(k) is element k of the scene's
+// plane records, (px, py, pz, 0) at 2j and (nx, ny, nz, 0) at 2j + 1.
+//   * the cheap part -- denom = dot(d, n), candidate iff !(denom > 1e-6) -- runs for every lane and every plane, as it did, and
+//     only STASHES the plane in the lane: its index and its denom, one select each.  Which lanes hold a stash is a wave mask, so
+//     the bookkeeping is scalar;
+//   * the division runs in dense passes: when a plane comes up for a lane whose stash is taken, and after the last plane, every
+//     lane with a stash reads ITS plane's two records by its own address, divides by the denom it kept (the same bits) and folds.
+//     Floor and ceiling are candidates of complementary sets of rays: tested plane by plane the division ran twice per trace on
+//     half-empty lanes, now once on full ones (the mirror box's six planes: three passes for six).  A pass runs only at a plane that
+//     has a candidate, or at the end for what is left, so there are never more passes than planes with a candidate -- what ran before.
+//   * the fold is the same fold: a lane's stash is always its earliest candidate not yet folded, so the lane folds its candidates in
+//     ascending index after all its spheres, with the same `<=`: ties keep the earlier primitive (a sphere before a plane at the same
+//     t, the first of two coincident planes).  A lane without a stash takes part in a pass with a denom of 1 -- no candidate, a
+//     Nothing, which replaces an accumulator that is still NaN and no other (+inf: see check_hit) -- as lanes that were no candidates
+//     of a tested plane always did.  A plane a lane is no candidate of is otherwise a Nothing that the lane skips, like every skipped
+//     element (see check_hit): it differs from the literal fold only where the final accumulator is a Just whose key is not < FLT_MAX
+//     -- which the callers detect and redo literally -- or where the accumulator is never filled (no sphere on the square-root path,
+//     no pass): just == false then, as in the literal fold, and every caller reads t and idx of a Just only.
+template <typename At>
+__device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, float &best_key, int &best_idx, bool &best_just,
+                                            unsigned int *diag = nullptr)
+{
+    int stash = 0;
+    float stash_denom = 1.0f;
+    unsigned long long stashed = 0ull;                       // the lanes that hold a stash
+    auto pass = [&]() {
+        diag::plane_pass(diag);
+        const float4 gp = at(2 * stash), gn = at(2 * stash + 1);
+        const float t = dot(mk(gp.x, gp.y, gp.z) - o, mk(gn.x, gn.y, gn.z)) / stash_denom;
+        const bool just = !(stash_denom > 1e-6f) && !(t < 0.0f);
+        const float key = just ? t : kInfinite;
+        if (!(best_key <= key)) { best_key = key; best_idx = ns + stash; best_just = just; }
+        stash_denom = 1.0f;
+        stashed = 0ull;
+    };
+    for (int j = 0; j < np; ++j) {
+        const float4 gn = at(2 * j + 1);
+        const float denom = dot(d, mk(gn.x, gn.y, gn.z));
+        const bool cand = !(denom > 1e-6f);
+        const unsigned long long cands = __ballot(cand);
+        diag::plane_test(diag);
+        if (cands & stashed) pass();
+        stash = cand ? j : stash;
+        stash_denom = cand ? denom : stash_denom;
+        stashed |= cands;
+    }
+    if (stashed) pass();
+}
+
 // check_hit is the same fold shaped for the SIMD:
 //   * the cheap part of every test (16 f32 operations for a sphere) runs for all lanes; the square
 //     root / division and the fold update run only when some lane of the wave can still be hit
@@ -175,9 +225,7 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
             P += 2;
         }
         if (i < ns) {
-            gb = P[1];
             sphere(ga, i);
-            ga = gb;
             P += 1;
         }
     } else
@@ -190,31 +238,14 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
             ga = S[i + 2];                                       // S has readable elements past the geometry
             sphere(gb, i + 1);
         }
-        if (i < ns) {
-            gb = S[i + 1];
-            sphere(ga, i);
-            ga = gb;
-        }
+        if (i < ns) sphere(ga, i);
     }
-    for (int j = 0; j < np; ++j) {
-        // distanceTo @Plane (Intersection.hs:57-62); ga holds (px, py, pz, 0)
-        float4 gn, g_next;
+    fold_planes([&](int k) -> float4 {
 #if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (STAGED) { gn = P[2 * j + 1]; g_next = P[2 * j + 2]; } else
+        if constexpr (STAGED) return P[k]; else
 #endif
-        { gn = S[ns + 2 * j + 1]; g_next = S[ns + 2 * j + 2]; }
-        const V3 nor = mk(gn.x, gn.y, gn.z);
-        const float denom = dot(d, nor);
-        const bool cand = !(denom > 1e-6f);
-        diag::plane_test(diag, cand);
-        if (__any(cand)) {
-            const float t = dot(mk(ga.x, ga.y, ga.z) - o, nor) / denom;
-            const bool just = cand && !(t < 0.0f);
-            const float key = just ? t : kInfinite;
-            if (!(best_key <= key)) { best_key = key; best_idx = ns + j; best_just = just; }
-        }
-        ga = g_next;
-    }
+        return S[ns + k];
+    }, ns, np, o, d, best_key, best_idx, best_just, diag);
     if (__builtin_expect(__any(best_just && !(best_key < kInfinite)), 0))
         return check_hit_exact(S, ns, np, o, d);
     HitSel best; best.t = best_key; best.idx = best_idx; best.just = best_just;

@@ -37,7 +37,8 @@ PTMI_PROBE unsigned int wave_max(unsigned int v)
 }
 
 // ---- check_hit: [16] sphere tests (per wave), [17] ... that took the square-root path, [18] candidate lanes, [19] active lanes,
-// [20] plane tests (per wave), [21] ... that took the division path
+// [20] plane tests (per wave: the cheap part, every plane), [21] dense passes run (per wave: the division, each lane on its own lowest
+// pending plane -- fold_planes, ptmi_device.h)
 #ifdef PTMI_SPHERE_STATS
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *work_counter) { return work_counter; }
 PTMI_PROBE void sphere_test(unsigned int *wc, bool cand)
@@ -50,18 +51,19 @@ PTMI_PROBE void sphere_test(unsigned int *wc, bool cand)
         atomicAdd(wc + 19, (unsigned int)__builtin_popcountll(am));
     }
 }
-PTMI_PROBE void plane_test(unsigned int *wc, bool cand)
+PTMI_PROBE void plane_test(unsigned int *wc)
 {
-    const unsigned long long cm = __ballot(cand), am = __ballot(1);
-    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(am)) {
-        atomicAdd(wc + 20, 1u);
-        if (cm) atomicAdd(wc + 21, 1u);
-    }
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 20, 1u);
+}
+PTMI_PROBE void plane_pass(unsigned int *wc)
+{
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 21, 1u);
 }
 #else
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *) { return nullptr; }
 PTMI_PROBE static void sphere_test(unsigned int *, bool) {}
-PTMI_PROBE static void plane_test(unsigned int *, bool) {}
+PTMI_PROBE static void plane_test(unsigned int *) {}
+PTMI_PROBE static void plane_pass(unsigned int *) {}
 #endif
 
 // ---- render Inline: [1] lane-trips, [2..4] lane participations in the shade round(s) and the trace round, [5] trips of the wave's

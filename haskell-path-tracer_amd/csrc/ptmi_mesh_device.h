@@ -121,19 +121,7 @@ template <typename ScenePtr>
 __device__ __forceinline__ void bvh_fold_planes(ScenePtr S, int ns, int np, V3 o, V3 d, float &best_key, int &best_idx, bool &best_just)
 {
     if (!best_just) { best_key = __builtin_nanf(""); best_idx = 0; }    // no sphere hit: check_hit's accumulator is still unfilled
-    for (int j = 0; j < np; ++j) {
-        // distanceTo @Plane (Intersection.hs:57-62), check_hit's fold
-        const float4 gp = S[ns + 2 * j], gn = S[ns + 2 * j + 1];
-        const V3 nor = mk(gn.x, gn.y, gn.z);
-        const float denom = dot(d, nor);
-        const bool cand = !(denom > 1e-6f);
-        if (__any(cand)) {
-            const float t = dot(mk(gp.x, gp.y, gp.z) - o, nor) / denom;
-            const bool just = cand && !(t < 0.0f);
-            const float key = just ? t : kInfinite;
-            if (!(best_key <= key)) { best_key = key; best_idx = ns + j; best_just = just; }
-        }
-    }
+    fold_planes([&](int k) -> float4 { return S[ns + k]; }, ns, np, o, d, best_key, best_idx, best_just);   // check_hit's fold
 }
 
 // THE TRIANGLE TEST (an extension: the reference has no triangle).  A record is (v0, nx) (v1, ny) (v2, nz), n the unit normal the host

@@ -112,8 +112,8 @@ def role_of(b, inner):
         return "sphere_candidate"
     if inner and has("v_cndmask_b32") and has("v_cmp_nle_f32") and b["valu"] <= 8 and not has("v_div_scale_f32"):
         return "sphere_candidate"                  # the fold update behind the square root
-    if has("v_div_scale_f32") and inner:
-        return "plane_test"
+    if has("v_div_scale_f32") and (inner or has("v_cmp_nle_f32")):
+        return "plane_test"                        # a dense pass of the plane fold: the division and the fold's compare (in the plane loop, and once behind it)
     if has("v_cvt_f64_f32") or has("v_cvt_i32_f64"):
         return "sincos_reduce"
     if has("v_fma_f64", "v_fmac_f64", "v_mul_f64"):
@@ -173,11 +173,11 @@ def main():
     # executions of ONE copy of a role's code per launch.  A role with k copies in the kernel (unrolled sites, the three sin/cos evaluations) runs
     # each copy (role executions / k) times; all copies hold the same instructions, so instructions per launch = mean static count x role executions
     e = execs or {}
-    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_candidate": e.get("sphere_sqrt_path"), "plane_test": e.get("plane_division_path"),
+    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_candidate": e.get("sphere_sqrt_path"), "plane_test": e.get("plane_passes", e.get("plane_division_path")),
                   "sincos_reduce": 3 * e["shade"] if e else None, "sincos_polynomial": 3 * e["shade"] if e else None, "hit_normal": None,
                   "rest_of_loop": e.get("trips"), "sqrt_slow": 0, "division_fallback": 0}
     what = {"sphere_test": "distanceTo @Sphere, the part every lane runs (16 f32 operations, the candidate test)", "sphere_candidate": "... its square root, t and the fold update, when a lane of the wave can be hit",
-            "plane_test": "distanceTo @Plane with its IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade",
+            "plane_test": "distanceTo @Plane: a dense pass of the plane fold (each lane on its own stashed plane), IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade",
             "sincos_polynomial": "sin/cos: the two f64 polynomials, sign and swap by bit operations", "hit_normal": "hit: the sphere normal's three divisions by one length",
             "rest_of_loop": "everything else in the loop, booked at ONE execution per trip: flags and masks, frozen check and finish, restart, draws, rotation, apply_bounce",
             "sqrt_slow": "compiler's scaled square root (a lane with 0 < x < 2^-96): practically never", "division_fallback": "compiler divisions behind range checks (huge or zero operands, inf / NaN): practically never"}
