@@ -61,6 +61,13 @@ SYMBOLS = {
     "ptmi_set_mesh_triangles": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_set_mesh_triangles_device": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_mesh_layout_morton": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "ptmi_update_spheres": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_update_spheres_device": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_set_bvh_spheres": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_set_bvh_spheres_device": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_bvh_refit_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_bvh_layout_morton": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_bvh_read_layout": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "ptmi_local_rows": (C.c_int, [_vp]),
@@ -101,6 +108,8 @@ SYMBOLS = {
     "ptmi_group_set_scene_mesh": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "ptmi_group_update_mesh_vertices": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_group_set_mesh_triangles": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_group_update_spheres": (C.c_int, [_vp, _vp, C.c_int]),
+    "ptmi_group_set_bvh_spheres": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_group_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_group_init_output": (C.c_int, [_vp, C.c_uint64]),
     "ptmi_group_reseed": (C.c_int, [_vp, C.c_uint64]),
@@ -198,6 +207,37 @@ def bvh_layout(spheres):
     if got < 0:
         raise PtmiError(got, "ptmi_bvh_layout")
     return nodes[:got].copy(), order
+
+
+def bvh_layout_morton(spheres):
+    """ptmi_bvh_layout_morton: the hierarchy ptmi_set_bvh_spheres builds on the device (host code, no device) -> (nodes, order) as
+    bvh_layout returns them."""
+    s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    nodes = np.zeros(max(1, s.size), BVH_NODE_DTYPE)
+    order = np.zeros(s.size, np.int32)
+    got = load_library().ptmi_bvh_layout_morton(_ptr(s) if s.size else None, s.size, _ptr(nodes), nodes.size, _ptr(order) if s.size else None)
+    if got < 0:
+        raise PtmiError(got, "ptmi_bvh_layout_morton")
+    return nodes[:got].copy(), order
+
+
+def bvh_refit_layout(spheres, nodes, order):
+    """ptmi_bvh_refit_layout: `nodes` and `order` of bvh_layout (or bvh_layout_morton) for the scene as set, refitted to the moved
+    `spheres` (host code, no device) -> the nodes with new boxes and inv_2r (a copy; ref and order are kept)."""
+    s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    out = np.array(nodes, dtype=BVH_NODE_DTYPE, copy=True).reshape(-1)
+    o = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+    rc = load_library().ptmi_bvh_refit_layout(_ptr(s) if s.size else None, s.size, _ptr(out), out.size, _ptr(o) if o.size else None)
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_bvh_refit_layout")
+    return out
+
+
+def _device_rows(t, words, what):
+    """a contiguous float32 device tensor of n * words elements (anything with is_cuda and data_ptr()) -> (pointer, n)"""
+    if not t.is_cuda or not t.is_contiguous() or "float32" not in str(t.dtype) or t.numel() % words:
+        raise ValueError("device %s must be a contiguous float32 tensor of shape (n, %d) on the context's device" % (what, words))
+    return _vp(t.data_ptr()), t.numel() // words
 
 
 def mesh_layout(triangles):
@@ -360,6 +400,48 @@ class Context:
         else:
             t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
             self._check(self._lib.ptmi_set_mesh_triangles(self._h, _ptr(t) if t.size else None, t.size))
+
+    def update_spheres(self, g):
+        """ptmi_update_spheres: move the spheres of a BVH or mesh scene and refit their hierarchy on the device.  g: (n, 4) float32 --
+        x, y, z, radius in the scene's index order -- a numpy array (host entry), or an object with is_cuda and data_ptr() such as a
+        contiguous float32 torch tensor on the context's device (device entry; the caller orders its writes before the context's
+        stream, and keeps the tensor until the stream has passed the call)."""
+        if hasattr(g, "is_cuda") and hasattr(g, "data_ptr"):
+            ptr, n = _device_rows(g, 4, "sphere geometry")
+            self._check(self._lib.ptmi_update_spheres_device(self._h, ptr if n else None, n))
+        else:
+            a = np.ascontiguousarray(g, dtype=np.float32)
+            if a.size % 4 or (a.size and (a.ndim != 2 or a.shape[1] != 4)):
+                raise ValueError("sphere geometry must have shape (n, 4), not %r" % (a.shape,))
+            self._check(self._lib.ptmi_update_spheres(self._h, _ptr(a) if a.size else None, a.size // 4))
+
+    def set_bvh_spheres(self, spheres):
+        """ptmi_set_bvh_spheres: replace the spheres of a BVH or mesh scene (any count) and build their hierarchy on the device.  spheres:
+        what set_scene_bvh accepts (host entry), or an object with is_cuda and data_ptr() such as a contiguous float32 torch tensor of
+        shape [n, 10] on the context's device, brdf_tag as its int32 bit pattern in word 8 (device entry)."""
+        if hasattr(spheres, "is_cuda") and hasattr(spheres, "data_ptr"):
+            ptr, n = _device_rows(spheres, 10, "spheres")
+            self._check(self._lib.ptmi_set_bvh_spheres_device(self._h, ptr if n else None, n))
+        else:
+            s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+            self._check(self._lib.ptmi_set_bvh_spheres(self._h, _ptr(s) if s.size else None, s.size))
+
+    def bvh_read_layout(self):
+        """ptmi_bvh_read_layout: the sphere hierarchy the device holds now -> (nodes, order), as bvh_layout returns them"""
+        n_nodes = self._lib.ptmi_bvh_read_layout(self._h, None, 0, None)      # (nothing copied: the size)
+        if n_nodes < 0:
+            self._check(n_nodes)
+        nodes = np.zeros(n_nodes, BVH_NODE_DTYPE)
+        got = self._lib.ptmi_bvh_read_layout(self._h, _ptr(nodes), nodes.size, None)      # (the nodes alone: their leaves say how long the order is)
+        if got < 0:
+            self._check(got)
+        ref = nodes["ref"][:got].reshape(-1).astype(np.int64)
+        n_spheres = int(np.sum((-1 - ref[ref < -1]) & 255))
+        order = np.zeros(max(1, n_spheres), np.int32)
+        got = self._lib.ptmi_bvh_read_layout(self._h, _ptr(nodes), nodes.size, _ptr(order))
+        if got < 0:
+            self._check(got)
+        return nodes[:got], order[:n_spheres].copy()
 
     def mesh_read_layout(self):
         """ptmi_mesh_read_layout: the triangle hierarchy the device holds now -> (nodes, order), as mesh_layout returns them"""
@@ -659,6 +741,16 @@ class Group:
         """ptmi_group_set_mesh_triangles: Context.set_mesh_triangles (host memory) on every member"""
         t = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
         self._check(self._lib.ptmi_group_set_mesh_triangles(self._h, _ptr(t) if t.size else None, t.size))
+
+    def update_spheres(self, g):
+        a = np.ascontiguousarray(g, dtype=np.float32)
+        if a.size % 4 or (a.size and (a.ndim != 2 or a.shape[1] != 4)):
+            raise ValueError("sphere geometry must have shape (n, 4), not %r" % (a.shape,))
+        self._check(self._lib.ptmi_group_update_spheres(self._h, _ptr(a) if a.size else None, a.size // 4))
+
+    def set_bvh_spheres(self, spheres):
+        s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+        self._check(self._lib.ptmi_group_set_bvh_spheres(self._h, _ptr(s) if s.size else None, s.size))
 
     def set_scene_mesh(self, spheres, triangles, planes):
         keep, args = _mesh_args(spheres, triangles, planes)

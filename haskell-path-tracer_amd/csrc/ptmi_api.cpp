@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ptmi_bvh.h"
+#include "ptmi_bvh_box.h"
 #include "ptmi_mesh.h"
 #include "ptmi_mesh_box.h"
 #include "ptmi_mesh_morton.h"
@@ -72,6 +73,14 @@ struct ptmi_ctx {
     size_t refit_leaf_pos_at = 0, refit_levels_at = 0;               // d_refit: byte offsets
     std::vector<int32_t> refit_level_first;
     bool fixed_has_glass = false;                                    // GLASS among the mesh scene's spheres and planes (ptmi_set_mesh_triangles keeps them)
+    // ... and what moving or replacing the spheres of a BVH or mesh scene needs (ptmi_update_spheres, ptmi_set_bvh_spheres): second blocks of
+    // d_bvh's and d_scene's layout that an update writes and then SWAPS with them (made at the first update: full copies, of which an
+    // update rewrites every box, every sphere record and the sphere rows); kSphWords result words and the sphere nodes level by level
+    // (BvhLevelPlan) in d_bvh_plan; the staged spheres of the host-pointer entries
+    DeviceBlock d_bvh_shadow, d_scene_shadow, d_bvh_plan, d_sphere_staging;
+    size_t bvh_nodes_f4 = 0;                                         // d_bvh: nodes | spheres in leaf order | indices
+    std::vector<int32_t> bvh_level_first;
+    bool planes_have_glass = false, triangles_have_glass = false;    // GLASS among what ptmi_set_bvh_spheres keeps
 
     DeviceBlock d_live;      // unsigned long long
     DeviceBlock d_work;      // unsigned int
@@ -168,7 +177,7 @@ struct ptmi_ctx {
     // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
     template <class F> void each_block(F &&f)
     {
-        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_mesh_shadow, &d_refit, &d_refit_staging, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_mesh_shadow, &d_refit, &d_refit_staging, &d_bvh_shadow, &d_scene_shadow, &d_bvh_plan, &d_sphere_staging, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
                                &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
                                &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
             f(*b);
@@ -279,6 +288,29 @@ void release_mesh_refit(ptmi_ctx *c)
     release(c->d_refit_staging);
     c->refit_level_first.clear();
 }
+
+// (with the BVH or mesh scene they belong to; the stream is drained)
+void release_sphere_update(ptmi_ctx *c)
+{
+    release(c->d_bvh_shadow);
+    release(c->d_scene_shadow);
+    release(c->d_bvh_plan);
+    release(c->d_sphere_staging);
+    c->bvh_level_first.clear();
+    c->bvh_nodes_f4 = 0;
+}
+
+// c->bvh's pointers into d_bvh, whichever of the two blocks that is (and the mesh scene's copy of them)
+void point_bvh_view(ptmi_ctx *c)
+{
+    const float4 *base = c->d_bvh.as<float4>();
+    c->bvh.nodes = base;
+    c->bvh.geom = base + c->bvh_nodes_f4;
+    c->bvh.index = reinterpret_cast<const int *>(base + c->bvh_nodes_f4 + (size_t)c->n_spheres);
+    if (c->scene_mesh) c->mesh.spheres = c->bvh;
+}
+
+constexpr size_t kBvhPlanLevelsAt = 256;                   // d_bvh_plan: the result words, then the nodes by level
 
 // c->mesh's pointers into d_mesh, whichever of the two blocks that is
 void point_mesh_view(ptmi_ctx *c)
@@ -1299,6 +1331,7 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     release(c->d_bvh);
     release(c->d_mesh);
     release_mesh_refit(c);
+    release_sphere_update(c);
     c->d_scene = fresh;
     c->scene_bvh = false; c->bvh = BvhView{};
     c->scene_mesh = false; c->mesh = MeshView{};
@@ -1344,33 +1377,43 @@ int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, c
     std::memcpy(hier.data(), bb.nodes.data(), bb.nodes.size() * sizeof(ptmi_bvh_node));
     for (int k = 0; k < n_spheres; ++k) hier[nodes_f4 + (size_t)k] = packed[(size_t)bb.order[(size_t)k]];
     if (n_spheres > 0) std::memcpy(&hier[nodes_f4 + geom_f4], bb.order.data(), (size_t)n_spheres * sizeof(int32_t));
+    // d_bvh_plan: what ptmi_update_spheres needs of this hierarchy (the result words, the nodes by level)
+    BvhLevelPlan plan;
+    bvh_level_plan(bb.nodes, plan);
+    std::vector<char> plan_block(kBvhPlanLevelsAt + plan.level_nodes.size() * sizeof(int32_t), 0);
+    std::memcpy(&plan_block[kBvhPlanLevelsAt], plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    // both blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
-    DeviceBlock fresh, fresh_bvh;
+    // all blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
+    DeviceBlock fresh, fresh_bvh, fresh_plan;
     PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
     hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_plan, plan_block.size());
     if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed` and `hier` die at return
-    if (e != hipSuccess) { release(fresh); release(fresh_bvh); PTMI_HIP(c, e); }
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_plan.p, plan_block.data(), fresh_plan.bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier` and `plan_block` die at return
+    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_plan); PTMI_HIP(c, e); }
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_mesh);
     release_mesh_refit(c);
+    release_sphere_update(c);
     c->d_scene = fresh;
     c->d_bvh = fresh_bvh;
+    c->d_bvh_plan = fresh_plan;
+    c->bvh_nodes_f4 = nodes_f4;
+    c->bvh_level_first = std::move(plan.level_first);
     c->scene_bvh = true;
     c->scene_mesh = false; c->mesh = MeshView{};
-    const float4 *base = c->d_bvh.as<float4>();
-    c->bvh.nodes = base;
-    c->bvh.geom = base + nodes_f4;
-    c->bvh.index = reinterpret_cast<const int *>(base + nodes_f4 + geom_f4);
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
     c->n_spheres = n_spheres; c->n_planes = n_planes;
+    point_bvh_view(c);
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
     ++c->scene_version;
     c->has_glass = false;
+    c->planes_have_glass = c->triangles_have_glass = false;
     for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
-    for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    for (int j = 0; j < n_planes; ++j) c->planes_have_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    c->has_glass |= c->planes_have_glass;
     return PTMI_OK;
 #endif
 }
@@ -1444,11 +1487,18 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     std::vector<char> refit(levels_at + plan.level_nodes.size() * sizeof(int32_t), 0);
     if (n_triangles > 0) std::memcpy(&refit[leaf_pos_at], plan.leaf_pos.data(), (size_t)n_triangles * sizeof(int32_t));
     std::memcpy(&refit[levels_at], plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t));
+    // d_bvh_plan: as ptmi_set_scene_bvh makes it
+    BvhLevelPlan sphere_plan;
+    bvh_level_plan(bb.nodes, sphere_plan);
+    std::vector<char> plan_block(kBvhPlanLevelsAt + sphere_plan.level_nodes.size() * sizeof(int32_t), 0);
+    std::memcpy(&plan_block[kBvhPlanLevelsAt], sphere_plan.level_nodes.data(), sphere_plan.level_nodes.size() * sizeof(int32_t));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     // all blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
-    DeviceBlock fresh, fresh_bvh, fresh_mesh, fresh_shadow, fresh_refit;
+    DeviceBlock fresh, fresh_bvh, fresh_mesh, fresh_shadow, fresh_refit, fresh_plan;
     PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
     hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_plan, plan_block.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh_plan.p, plan_block.data(), fresh_plan.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = allocate(fresh_mesh, tri.size() * sizeof(float4));
     if (e == hipSuccess) e = allocate(fresh_shadow, tri.size() * sizeof(float4));
     if (e == hipSuccess) e = allocate(fresh_refit, refit.size());
@@ -1459,13 +1509,17 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     if (e == hipSuccess) e = hipMemcpyAsync(fresh_shadow.p, fresh_mesh.p, fresh_mesh.bytes, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(fresh_refit.p, refit.data(), fresh_refit.bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier`, `tri` and `refit` die at return
-    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); PTMI_HIP(c, e); }
+    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); release(fresh_plan); PTMI_HIP(c, e); }
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_mesh);
     release_mesh_refit(c);
+    release_sphere_update(c);
     c->d_scene = fresh;
     c->d_bvh = fresh_bvh;
+    c->d_bvh_plan = fresh_plan;
+    c->bvh_nodes_f4 = nodes_f4;
+    c->bvh_level_first = std::move(sphere_plan.level_first);
     c->d_mesh = fresh_mesh;
     c->d_mesh_shadow = fresh_shadow;
     c->d_refit = fresh_refit;
@@ -1474,25 +1528,24 @@ int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, 
     c->refit_level_first = std::move(plan.level_first);
     c->scene_bvh = false;
     c->scene_mesh = true;
-    const float4 *base = c->d_bvh.as<float4>();
     c->bvh = BvhView{};
-    c->bvh.nodes = base;
-    c->bvh.geom = base + nodes_f4;
-    c->bvh.index = reinterpret_cast<const int *>(base + nodes_f4 + geom_f4);
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
     c->mesh = MeshView{};
-    c->mesh.spheres = c->bvh;
+    c->n_spheres = n_spheres; c->n_planes = n_planes;
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
+    point_bvh_view(c);                                     // (and mesh.spheres)
     point_mesh_view(c);
     c->mesh.n_triangles = n_triangles;
     c->mesh.n_kept = (int)kept;
     for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = mb.lo[a]; c->mesh.hi[a] = mb.hi[a]; }
-    c->n_spheres = n_spheres; c->n_planes = n_planes;
     ++c->scene_version;
     c->has_glass = false;
+    c->planes_have_glass = c->triangles_have_glass = false;
     for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
-    for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    for (int j = 0; j < n_planes; ++j) c->planes_have_glass |= planes[j].brdf_tag == PTMI_GLASS;
+    c->has_glass |= c->planes_have_glass;
     c->fixed_has_glass = c->has_glass;
-    for (int k = 0; k < n_triangles; ++k) c->has_glass |= triangles[k].brdf_tag == PTMI_GLASS;
+    for (int k = 0; k < n_triangles; ++k) c->triangles_have_glass |= triangles[k].brdf_tag == PTMI_GLASS;
+    c->has_glass |= c->triangles_have_glass;
     return PTMI_OK;
 #endif
 }
@@ -1642,6 +1695,10 @@ static int set_mesh_triangles_locked(ptmi_ctx *c, const float *d_triangles, int 
     release(c->d_mesh);
     release(c->d_mesh_shadow);
     release(c->d_refit);
+    // (the second scene block of ptmi_update_spheres was a copy of the block that goes, with the old triangles' materials: the next
+    // update makes its pair afresh)
+    release(c->d_bvh_shadow);
+    release(c->d_scene_shadow);
     c->d_scene = fresh;
     c->d_mesh = fresh_mesh;
     c->d_mesh_shadow = fresh_shadow;
@@ -1653,7 +1710,8 @@ static int set_mesh_triangles_locked(ptmi_ctx *c, const float *d_triangles, int 
     c->mesh.n_triangles = n;
     c->mesh.n_kept = kept;
     for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = lo[a]; c->mesh.hi[a] = hi[a]; }
-    c->has_glass = c->fixed_has_glass || got[kBuildGlass] != 0;
+    c->triangles_have_glass = got[kBuildGlass] != 0;
+    c->has_glass = c->fixed_has_glass || c->triangles_have_glass;
     ++c->scene_version;
     return PTMI_OK;
 }
@@ -1708,6 +1766,212 @@ int ptmi_mesh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, 
                          {const_cast<int *>(c->mesh.index), order, kept * sizeof(int32_t)}};
     PTMI_HIP(c, copy_to_host(c, spans, 2));
     if (n_kept) *n_kept = (int)kept;
+    return (int)n_nodes;
+}
+
+// Moving the spheres of the current BVH or mesh scene (see include/ptmi.h).  One validation path, on the device: the check kernel reads the
+// new geometry only; the host reads its verdict and the new box of the centres back with the call's ONE synchronisation; only then are
+// the writing kernels enqueued -- into the second hierarchy and scene blocks, which become the scene's when all of them are out.  c->mu is held.
+static int update_spheres_locked(ptmi_ctx *c, const float *d_geometry, int n)
+{
+    if (n == 0) return PTMI_OK;                            // (a scene without spheres: nothing moves)
+    unsigned int *result = c->d_bvh_plan.as<unsigned int>();
+    const int32_t *level_nodes = reinterpret_cast<const int32_t *>(c->d_bvh_plan.as<char>() + kBvhPlanLevelsAt);
+    unsigned int got[kSphWords];
+    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kSphHi * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(result + kSphHi, 0, (kSphWords - kSphHi) * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, launch_bvh_check(d_geometry, 4, n, result, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    if (got[kSphError] != 0xffffffffu)
+        return fail(c, PTMI_EINVAL, "sphere " + std::to_string(got[kSphError] >> 2) + ": its position, radius or radius^2 is not finite: a box cannot bound it");
+    if (c->d_bvh_shadow.bytes != c->d_bvh.bytes || c->d_scene_shadow.bytes != c->d_scene.bytes || !c->d_bvh_shadow.p || !c->d_scene_shadow.p) {
+        // (after the verdict: a refused update allocates nothing)  The second blocks start as copies of the scene's: an update rewrites
+        // every box, every sphere record and every sphere row of them; the references, the indices, the planes and the materials never
+        // move -- and whatever replaces d_scene or d_bvh releases the pair
+        release(c->d_bvh_shadow);
+        release(c->d_scene_shadow);
+        hipError_t e = allocate(c->d_bvh_shadow, c->d_bvh.bytes);
+        if (e == hipSuccess) e = allocate(c->d_scene_shadow, c->d_scene.bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_bvh_shadow.p, c->d_bvh.p, c->d_bvh.bytes, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_scene_shadow.p, c->d_scene.p, c->d_scene.bytes, hipMemcpyDeviceToDevice, c->stream);
+        if (e != hipSuccess) { release(c->d_bvh_shadow); release(c->d_scene_shadow); PTMI_HIP(c, e); }
+    }
+    float4 *shadow = c->d_bvh_shadow.as<float4>();
+    float4 *geom = shadow + c->bvh_nodes_f4;
+    const int32_t *order = reinterpret_cast<const int32_t *>(geom + (size_t)n);
+    PTMI_HIP(c, launch_bvh_records(d_geometry, 4, n, order, geom, c->d_scene_shadow.as<float4>(), nullptr, c->stream));
+    for (size_t lv = 0; lv + 1 < c->bvh_level_first.size(); ++lv)
+        PTMI_HIP(c, launch_bvh_level(shadow, d_geometry, 4, n, order, level_nodes + c->bvh_level_first[lv], c->bvh_level_first[lv + 1] - c->bvh_level_first[lv], c->stream));
+    std::swap(c->d_bvh, c->d_bvh_shadow);
+    std::swap(c->d_scene, c->d_scene_shadow);
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = ordered_value(got[kSphLo + a]); c->bvh.hi[a] = ordered_value(got[kSphHi + a]); }
+    point_bvh_view(c);
+    ++c->scene_version;
+    return PTMI_OK;
+}
+
+static int update_spheres_refusal(ptmi_ctx *c, const float *geometry, int n_spheres)
+{
+    if (!c->scene_bvh && !c->scene_mesh)
+        return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh): there is no hierarchy to refit");
+    if (n_spheres != c->n_spheres)
+        return fail(c, PTMI_EINVAL, "the scene has " + std::to_string(c->n_spheres) + " spheres, not " + std::to_string(n_spheres) +
+                                        ": an update moves spheres, it does not change their count (ptmi_set_bvh_spheres does)");
+    if (n_spheres > 0 && !geometry) return fail(c, PTMI_EINVAL, "bad sphere arguments");
+    return PTMI_OK;
+}
+
+int ptmi_update_spheres_device(ptmi_ctx *c, const float *d_geometry, int n_spheres)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = update_spheres_refusal(c, d_geometry, n_spheres)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    return update_spheres_locked(c, d_geometry, n_spheres);
+}
+
+int ptmi_update_spheres(ptmi_ctx *c, const float *geometry, int n_spheres)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = update_spheres_refusal(c, geometry, n_spheres)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    if (n_spheres > 0) {
+        const size_t bytes = (size_t)n_spheres * 4 * sizeof(float);
+        if (int rc = grow(c, c->d_sphere_staging, bytes, "sphere staging")) return rc;
+        CopySpan span{c->d_sphere_staging.p, const_cast<float *>(geometry), bytes};
+        PTMI_HIP(c, copy_to_device(c, &span, 1));
+    }
+    return update_spheres_locked(c, c->d_sphere_staging.as<float>(), n_spheres);
+}
+
+// New spheres for the current BVH or mesh scene (see include/ptmi.h).  The check kernel reads the new spheres only; the host reads its
+// verdict, the box of the centres and the GLASS flag back together (the first synchronisation); then fresh blocks -- the scene block for
+// the new count, the hierarchy, its plan -- are filled on the stream and become the scene's when all of it is through (the second).  c->mu is held.
+static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
+{
+    unsigned int *result = c->d_bvh_plan.as<unsigned int>();
+    unsigned int got[kSphWords];
+    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kSphHi * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, hipMemsetAsync(result + kSphHi, 0, (kSphWords - kSphHi) * sizeof(unsigned int), c->stream));
+    PTMI_HIP(c, launch_bvh_check(d_spheres, 10, n, result, c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    if (got[kSphError] != 0xffffffffu) {
+        const std::string who = "sphere " + std::to_string(got[kSphError] >> 2);
+        switch (got[kSphError] & 3u) {
+        case kSphBadGeometry: return fail(c, PTMI_EINVAL, who + ": its position, radius or radius^2 is not finite: a box cannot bound it");
+        case kSphBadMaterial: return fail(c, PTMI_EINVAL, who + ": its colour, illuminance or brdf_param is not finite");
+        default: return fail(c, PTMI_EINVAL, who + ": unknown brdf_tag");
+        }
+    }
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    if (n > 0)
+        for (int a = 0; a < 3; ++a) { lo[a] = ordered_value(got[kSphLo + a]); hi[a] = ordered_value(got[kSphHi + a]); }
+    // the topology and its levels are functions of the count alone (ptmi_mesh_morton.h)
+    std::vector<ptmi_bvh_node> topology;
+    BvhLevelPlan plan;
+    morton_topology(n, topology);
+    bvh_level_plan(topology, plan);
+    const size_t old_ns = (size_t)c->n_spheres, np = (size_t)c->n_planes, nt = c->scene_mesh ? (size_t)c->mesh.n_triangles : 0, ns = (size_t)n;
+    const size_t nodes_f4 = topology.size() * 4;
+    DeviceBlock fresh, fresh_bvh, fresh_plan, sort;
+    auto undo = [&]() { release(fresh); release(fresh_bvh); release(fresh_plan); release(sort); };
+    hipError_t e = allocate(fresh, (ns + 2 * np + 2 * (ns + np) + 2 * nt) * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_bvh, (nodes_f4 + ns + (ns + 3) / 4) * sizeof(float4));
+    if (e == hipSuccess) e = allocate(fresh_plan, kBvhPlanLevelsAt + plan.level_nodes.size() * sizeof(int32_t));
+    if (e == hipSuccess && n > 0) e = allocate(sort, mesh_build_sort_bytes(n));
+    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
+    float4 *scene = fresh.as<float4>(), *nodes = fresh_bvh.as<float4>(), *geom = nodes + nodes_f4;
+    const float4 *old_scene = c->d_scene.as<float4>();
+    int32_t *order = reinterpret_cast<int32_t *>(geom + ns);
+    int32_t *level_nodes = reinterpret_cast<int32_t *>(fresh_plan.as<char>() + kBvhPlanLevelsAt);
+    // the planes' rows, and the materials of planes and triangles, move to the offsets of the new count
+    if (np > 0) e = hipMemcpyAsync(scene + ns, old_scene + old_ns, 2 * np * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && np + nt > 0)
+        e = hipMemcpyAsync(scene + ns + 2 * np + 2 * ns, old_scene + old_ns + 2 * np + 2 * old_ns, 2 * (np + nt) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) {
+        CopySpan spans[2] = {{nodes, topology.data(), topology.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
+        e = copy_to_device(c, spans, 2);
+    }
+    if (e == hipSuccess) e = launch_bvh_build_order(d_spheres, n, lo, hi, sort.p, order, c->stream);
+    if (e == hipSuccess) e = launch_bvh_records(d_spheres, 10, n, order, geom, scene, scene + ns + 2 * np, c->stream);
+    for (size_t lv = 0; lv + 1 < plan.level_first.size() && e == hipSuccess; ++lv)
+        e = launch_bvh_level(nodes, d_spheres, 10, n, order, level_nodes + plan.level_first[lv], plan.level_first[lv + 1] - plan.level_first[lv], c->stream);
+    // the stream is drained before the old blocks and the sort's scratch go (grow()'s rule), and a launch that failed on the device is
+    // seen while the old scene still stands; `topology` and `plan` die at return
+    const hipError_t drained = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = drained;
+    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
+    release(sort);
+    release(c->d_scene);
+    release(c->d_bvh);
+    release(c->d_bvh_shadow);
+    release(c->d_scene_shadow);
+    release(c->d_bvh_plan);
+    c->d_scene = fresh;
+    c->d_bvh = fresh_bvh;
+    c->d_bvh_plan = fresh_plan;
+    c->bvh_nodes_f4 = nodes_f4;
+    c->bvh_level_first = std::move(plan.level_first);
+    c->n_spheres = n;
+    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = lo[a]; c->bvh.hi[a] = hi[a]; }
+    point_bvh_view(c);
+    c->fixed_has_glass = c->planes_have_glass || got[kSphGlass] != 0;
+    c->has_glass = c->fixed_has_glass || c->triangles_have_glass;
+    ++c->scene_version;
+    return PTMI_OK;
+}
+
+static int set_bvh_spheres_refusal(ptmi_ctx *c, const void *spheres, int n_spheres)
+{
+    if (!c->scene_bvh && !c->scene_mesh)
+        return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh): there are no spheres to replace");
+    if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(c, PTMI_EINVAL, "bad sphere arguments");
+    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
+    if (n_spheres == 0 && c->n_planes == 0 && !(c->scene_mesh && c->mesh.n_triangles > 0))
+        return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
+    return PTMI_OK;
+}
+
+int ptmi_set_bvh_spheres_device(ptmi_ctx *c, const ptmi_sphere *d_spheres, int n_spheres)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = set_bvh_spheres_refusal(c, d_spheres, n_spheres)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    return set_bvh_spheres_locked(c, reinterpret_cast<const float *>(d_spheres), n_spheres);
+}
+
+int ptmi_set_bvh_spheres(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (int rc = set_bvh_spheres_refusal(c, spheres, n_spheres)) return rc;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    if (n_spheres > 0) {
+        const size_t bytes = (size_t)n_spheres * sizeof(ptmi_sphere);
+        if (int rc = grow(c, c->d_sphere_staging, bytes, "sphere staging")) return rc;
+        CopySpan span{c->d_sphere_staging.p, const_cast<ptmi_sphere *>(spheres), bytes};
+        PTMI_HIP(c, copy_to_device(c, &span, 1));
+    }
+    return set_bvh_spheres_locked(c, c->d_sphere_staging.as<float>(), n_spheres);
+}
+
+int ptmi_bvh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, int32_t *order)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (!c->scene_bvh && !c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh)");
+    const size_t n_nodes = c->bvh_nodes_f4 / 4, ns = (size_t)c->n_spheres;
+    if (!nodes && !order) return (int)n_nodes;               // the size only
+    if (!nodes) return fail(c, PTMI_EINVAL, "bad layout arguments");
+    if (node_capacity < 0 || (size_t)node_capacity < n_nodes) return fail(c, PTMI_ELIMIT, "node_capacity is smaller than the hierarchy");
+    PTMI_HIP(c, hipSetDevice(c->device));
+    CopySpan spans[2] = {{const_cast<float4 *>(c->bvh.nodes), nodes, n_nodes * sizeof(ptmi_bvh_node)},
+                         {const_cast<int *>(c->bvh.index), order, order ? ns * sizeof(int32_t) : 0}};      // (no order: the nodes alone)
+    PTMI_HIP(c, copy_to_host(c, spans, 2));
     return (int)n_nodes;
 }
 

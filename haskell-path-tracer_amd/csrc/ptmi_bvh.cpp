@@ -14,6 +14,8 @@
 //   * what scales with the distance P from the ray origin to the scene (the cancellation in l.l - tca^2) is a margin the traversal
 //     adds per ray (check_hit_bvh), using the smallest radius under each child (ptmi_bvh_node.inv_2r).
 #include "ptmi_bvh.h"
+#include "ptmi_bvh_box.h"
+#include "ptmi_mesh_morton.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,77 +27,37 @@ namespace ptmi {
 
 namespace {
 
-constexpr double kRelPad = 1.0 / 256.0, kAbsPad = 1.0 / 1048576.0;
 constexpr int kLeafCap = 255;                    // what a leaf reference can encode
-
-double pad_of(const ptmi_sphere &s)
-{
-    const double r = std::fabs((double)s.radius);
-    const double m = std::max({std::fabs((double)s.position[0]), std::fabs((double)s.position[1]), std::fabs((double)s.position[2]), r});
-    return r * (1.0 + kRelPad) + kAbsPad * m;
-}
-
-float round_up(double v)
-{
-    float f = (float)v;
-    if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-    return f;
-}
+                                                 // (the box arithmetic is ptmi_bvh_box.h's, shared with the refit and the device)
 
 struct Builder {
     const ptmi_sphere *s;
-    std::vector<double> pad;
     std::vector<int32_t> idx;
     std::vector<ptmi_bvh_node> nodes;
-
-    // the stored (centre, half) of a box holding [lo, hi], rounded outwards
-    static void store(ptmi_bvh_node &nd, int c, const double lo[3], const double hi[3])
-    {
-        for (int a = 0; a < 3; ++a) {
-            const float cf = (float)(0.5 * (lo[a] + hi[a]));
-            nd.center[c][a] = cf;
-            nd.half[c][a] = round_up(std::max(hi[a] - (double)cf, (double)cf - lo[a]));
-        }
-    }
 
     // child c of node `nd` is inner node `inner`: its box is the union of that node's two boxes as STORED (so that boxes nest exactly)
     void set_box_of_node(ptmi_bvh_node &nd, int c, int inner) const
     {
         const ptmi_bvh_node &in = nodes[(size_t)inner];
         double lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) { lo[a] = std::numeric_limits<double>::infinity(); hi[a] = -lo[a]; }
-        for (int k = 0; k < 2; ++k) {
-            if (in.ref[k] == -1) continue;
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::min(lo[a], (double)in.center[k][a] - (double)in.half[k][a]);
-                hi[a] = std::max(hi[a], (double)in.center[k][a] + (double)in.half[k][a]);
-            }
-        }
-        store(nd, c, lo, hi);
-        nd.inv_2r[c] = std::max(in.ref[0] == -1 ? 0.0f : in.inv_2r[0], in.ref[1] == -1 ? 0.0f : in.inv_2r[1]);
+        bvh_inner_box(lo, hi, in.center, in.half, in.ref[0], in.ref[1]);
+        bvh_store(nd.center[c], nd.half[c], lo, hi);
+        nd.inv_2r[c] = bvh_inner_inv_2r(in.inv_2r[0], in.inv_2r[1], in.ref[0], in.ref[1]);
     }
 
     // child c of node `nd` is the leaf idx[b, e)
     void set_box(ptmi_bvh_node &nd, int c, int b, int e) const
     {
         if (b == e) {
-            for (int a = 0; a < 3; ++a) { nd.center[c][a] = 0.0f; nd.half[c][a] = -1.0f; }
-            nd.inv_2r[c] = 0.0f;
+            bvh_empty_child(nd.center[c], nd.half[c], nd.inv_2r[c]);
             return;
         }
         double lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) { lo[a] = std::numeric_limits<double>::infinity(); hi[a] = -lo[a]; }
+        box_empty(lo, hi);
         double r_min = std::numeric_limits<double>::infinity();
-        for (int k = b; k < e; ++k) {
-            const ptmi_sphere &sp = s[idx[k]];
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::min(lo[a], (double)sp.position[a] - pad[idx[k]]);
-                hi[a] = std::max(hi[a], (double)sp.position[a] + pad[idx[k]]);
-            }
-            r_min = std::min(r_min, std::fabs((double)sp.radius));
-        }
-        store(nd, c, lo, hi);
-        nd.inv_2r[c] = r_min > 0.0 ? round_up(1.0 / (2.0 * r_min)) : std::numeric_limits<float>::infinity();
+        for (int k = b; k < e; ++k) bvh_leaf_join(lo, hi, r_min, s[idx[k]].position, s[idx[k]].radius);
+        bvh_store(nd.center[c], nd.half[c], lo, hi);
+        nd.inv_2r[c] = bvh_leaf_inv_2r(r_min);
     }
 
     // the reference to a child holding idx[b, e) at `level` (the level the child would have as an inner node)
@@ -150,17 +112,10 @@ int bvh_build(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why
     auto refuse = [&](int code, const char *msg) { if (why) *why = msg; return code; };
     if (n < 0 || (n > 0 && !spheres)) return refuse(PTMI_EINVAL, "bad sphere arguments");
     if (n > PTMI_MAX_BVH_SPHERES) return refuse(PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
-    for (int i = 0; i < n; ++i) {
-        const ptmi_sphere &sp = spheres[i];
-        const float r2 = sp.radius * sp.radius;     // what the device tests against (pack_scene)
-        if (!std::isfinite(sp.position[0]) || !std::isfinite(sp.position[1]) || !std::isfinite(sp.position[2]) || !std::isfinite(sp.radius) ||
-            !std::isfinite(r2))
-            return refuse(PTMI_EINVAL, "a sphere's position, radius or radius^2 is not finite: a box cannot bound it");
-    }
+    for (int i = 0; i < n; ++i)
+        if (bvh_sphere_refusal(spheres[i])) return refuse(PTMI_EINVAL, "a sphere's position, radius or radius^2 is not finite: a box cannot bound it");
     Builder bd;
     bd.s = spheres;
-    bd.pad.resize((size_t)n);
-    for (int i = 0; i < n; ++i) bd.pad[(size_t)i] = pad_of(spheres[i]);
     bd.idx.resize((size_t)n);
     std::iota(bd.idx.begin(), bd.idx.end(), 0);
     bd.nodes.reserve((size_t)std::max(1, n / 2));
@@ -177,6 +132,117 @@ int bvh_build(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why
     return PTMI_OK;
 }
 
+void bvh_level_plan(const std::vector<ptmi_bvh_node> &nodes, BvhLevelPlan &out)
+{
+    // children have larger ids than their parent (child() appends before it fills): one ascending pass gives every level
+    const size_t n = nodes.size();
+    std::vector<int32_t> level(n, 0);
+    int deepest = 0;
+    for (size_t id = 0; id < n; ++id)
+        for (int c = 0; c < 2; ++c)
+            if (nodes[id].ref[c] >= 0) {
+                level[(size_t)nodes[id].ref[c]] = level[id] + 1;
+                deepest = std::max(deepest, level[id] + 1);
+            }
+    std::vector<int32_t> count((size_t)deepest + 2, 0);
+    for (size_t id = 0; id < n; ++id) ++count[(size_t)(deepest - level[id]) + 1];
+    for (size_t k = 1; k < count.size(); ++k) count[k] += count[k - 1];
+    out.level_first = count;
+    out.level_nodes.assign(n, 0);
+    for (size_t id = 0; id < n; ++id) out.level_nodes[(size_t)count[(size_t)(deepest - level[id])]++] = (int32_t)id;
+}
+
+const char *bvh_sphere_refusal(const ptmi_sphere &sp)
+{
+    const float r2 = sp.radius * sp.radius;     // what the device tests against (pack_scene)
+    if (!std::isfinite(sp.position[0]) || !std::isfinite(sp.position[1]) || !std::isfinite(sp.position[2]) || !std::isfinite(sp.radius) ||
+        !std::isfinite(r2))
+        return "its position, radius or radius^2 is not finite: a box cannot bound it";
+    return nullptr;
+}
+
+int bvh_refit(const ptmi_sphere *spheres, int n, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order, std::string *why)
+{
+    auto refuse = [&](const std::string &msg) { if (why) *why = msg; return (int)PTMI_EINVAL; };
+    if (n < 0 || n_nodes < 1 || !nodes || (n > 0 && (!spheres || !order))) return refuse("bad refit arguments");
+    // the topology must be one ptmi_bvh_layout can have made: every node but the root referred to once, by a node before it; the
+    // leaves a partition of the leaf order; the leaf order a permutation of the spheres
+    long long inner = 0, in_leaves = 0;
+    for (int id = 0; id < n_nodes; ++id)
+        for (int c = 0; c < 2; ++c) {
+            const int32_t ref = nodes[id].ref[c];
+            if (ref >= 0) {
+                if (ref <= id || ref >= n_nodes) return refuse("the nodes are not a hierarchy of ptmi_bvh_layout (a child reference out of range: wrong n_nodes?)");
+                ++inner;
+            } else if (ref != -1) {
+                const uint32_t v = (uint32_t)(-1 - ref);
+                if ((long long)(v >> 8) + (v & 255u) > n) return refuse("a leaf lies beyond the leaf order (wrong n_spheres?)");
+                in_leaves += v & 255u;
+            }
+        }
+    if (inner != n_nodes - 1 || in_leaves != n) return refuse("the nodes and the leaf order do not belong together (wrong n_nodes or n_spheres?)");
+    std::vector<char> seen((size_t)n, 0);
+    for (int k = 0; k < n; ++k) {
+        if (order[k] < 0 || order[k] >= n || seen[(size_t)order[k]]) return refuse("the leaf order is not a permutation of the spheres");
+        seen[(size_t)order[k]] = 1;
+    }
+    for (int i = 0; i < n; ++i)
+        if (const char *bad = bvh_sphere_refusal(spheres[i])) return refuse("sphere " + std::to_string(i) + ": " + bad);
+    for (int id = n_nodes - 1; id >= 0; --id) {
+        ptmi_bvh_node &nd = nodes[id];
+        for (int c = 0; c < 2; ++c) {
+            const int32_t ref = nd.ref[c];
+            if (ref == -1) { bvh_empty_child(nd.center[c], nd.half[c], nd.inv_2r[c]); continue; }
+            double lo[3], hi[3];
+            if (ref >= 0) {
+                const ptmi_bvh_node &in = nodes[ref];
+                bvh_inner_box(lo, hi, in.center, in.half, in.ref[0], in.ref[1]);
+                nd.inv_2r[c] = bvh_inner_inv_2r(in.inv_2r[0], in.inv_2r[1], in.ref[0], in.ref[1]);
+            } else {
+                const uint32_t v = (uint32_t)(-1 - ref);
+                double r_min = std::numeric_limits<double>::infinity();
+                box_empty(lo, hi);
+                for (uint32_t k = v >> 8; k < (v >> 8) + (v & 255u); ++k) bvh_leaf_join(lo, hi, r_min, spheres[order[k]].position, spheres[order[k]].radius);
+                nd.inv_2r[c] = bvh_leaf_inv_2r(r_min);
+            }
+            bvh_store(nd.center[c], nd.half[c], lo, hi);
+        }
+    }
+    return PTMI_OK;
+}
+
+// ptmi_bvh_layout_morton / the specification of ptmi_set_bvh_spheres: bvh_build's and the scene calls' refusals; the leaf order by
+// (Morton key of the centre, index) and the topology of the count (ptmi_mesh_morton.h); the boxes by the refit over that topology.
+int bvh_build_morton(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why)
+{
+    auto refuse = [&](int code, const std::string &msg) { if (why) *why = msg; return code; };
+    if (n < 0 || (n > 0 && !spheres)) return refuse(PTMI_EINVAL, "bad sphere arguments");
+    if (n > PTMI_MAX_BVH_SPHERES) return refuse(PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
+    for (int i = 0; i < n; ++i) {
+        const ptmi_sphere &sp = spheres[i];
+        const std::string who = "sphere " + std::to_string(i) + ": ";
+        if (const char *bad = bvh_sphere_refusal(sp)) return refuse(PTMI_EINVAL, who + bad);
+        if (!std::isfinite(sp.color[0]) || !std::isfinite(sp.color[1]) || !std::isfinite(sp.color[2]) || !std::isfinite(sp.illuminance) ||
+            !std::isfinite(sp.brdf_param))
+            return refuse(PTMI_EINVAL, who + "its colour, illuminance or brdf_param is not finite");
+        if (sp.brdf_tag < PTMI_MATTE || sp.brdf_tag > PTMI_GLASS) return refuse(PTMI_EINVAL, who + "unknown brdf_tag");
+    }
+    for (int a = 0; a < 3; ++a) { out.lo[a] = 0.0f; out.hi[a] = 0.0f; }
+    if (n > 0) {
+        for (int a = 0; a < 3; ++a) { out.lo[a] = std::numeric_limits<float>::infinity(); out.hi[a] = -out.lo[a]; }
+        for (int i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) { out.lo[a] = std::min(out.lo[a], spheres[i].position[a]); out.hi[a] = std::max(out.hi[a], spheres[i].position[a]); }
+    }
+    std::vector<uint64_t> key((size_t)n, 0);
+    for (int i = 0; i < n; ++i) key[(size_t)i] = morton_key(spheres[i].position, spheres[i].position, spheres[i].position, out.lo, out.hi);
+    out.order.resize((size_t)n);
+    std::iota(out.order.begin(), out.order.end(), 0);
+    const uint64_t *kp = key.data();
+    std::sort(out.order.begin(), out.order.end(), [kp](int32_t x, int32_t y) { return kp[x] < kp[y] || (kp[x] == kp[y] && x < y); });
+    morton_topology(n, out.nodes);
+    return bvh_refit(spheres, n, out.nodes.data(), (int)out.nodes.size(), out.order.data(), why);
+}
+
 }  // namespace ptmi
 
 extern "C" int ptmi_bvh_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order)
@@ -189,4 +255,26 @@ extern "C" int ptmi_bvh_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_b
     std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(ptmi_bvh_node));
     if (n_spheres > 0) std::memcpy(order, b.order.data(), (size_t)n_spheres * sizeof(int32_t));
     return (int)b.nodes.size();
+}
+
+extern "C" int ptmi_bvh_layout_morton(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order)
+{
+    if (n_spheres < 0 || !nodes || (n_spheres > 0 && (!spheres || !order))) return PTMI_EINVAL;
+    if (n_spheres > PTMI_MAX_BVH_SPHERES) return PTMI_ELIMIT;
+    ptmi::BvhBuild b;
+    if (int rc = ptmi::bvh_build_morton(spheres, n_spheres, b, nullptr)) return rc;
+    if (node_capacity < 0 || (size_t)node_capacity < b.nodes.size()) return PTMI_ELIMIT;
+    std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(ptmi_bvh_node));
+    if (n_spheres > 0) std::memcpy(order, b.order.data(), (size_t)n_spheres * sizeof(int32_t));
+    return (int)b.nodes.size();
+}
+
+extern "C" int ptmi_bvh_refit_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order)
+{
+    if (n_spheres < 0 || n_nodes < 1 || !nodes) return PTMI_EINVAL;
+    // refitted aside: a refusal writes nothing
+    std::vector<ptmi_bvh_node> work(nodes, nodes + n_nodes);
+    if (int rc = ptmi::bvh_refit(spheres, n_spheres, work.data(), n_nodes, order, nullptr)) return rc;
+    std::memcpy(nodes, work.data(), work.size() * sizeof(ptmi_bvh_node));
+    return PTMI_OK;
 }

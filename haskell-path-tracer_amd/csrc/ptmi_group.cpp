@@ -239,6 +239,24 @@ int ptmi_group_set_mesh_triangles(ptmi_group *g, const ptmi_triangle *triangles,
     return PTMI_OK;
 }
 
+int ptmi_group_update_spheres(ptmi_group *g, const float *geometry, int n_spheres)
+{
+    if (!g) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(g->mu);
+    for (size_t i = 0; i < g->members.size(); ++i)
+        if (int rc = ptmi_update_spheres(g->members[i], geometry, n_spheres)) return member_fail(g, (int)i, rc);
+    return PTMI_OK;
+}
+
+int ptmi_group_set_bvh_spheres(ptmi_group *g, const ptmi_sphere *spheres, int n_spheres)
+{
+    if (!g) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(g->mu);
+    for (size_t i = 0; i < g->members.size(); ++i)
+        if (int rc = ptmi_set_bvh_spheres(g->members[i], spheres, n_spheres)) return member_fail(g, (int)i, rc);
+    return PTMI_OK;
+}
+
 int ptmi_group_resize(ptmi_group *g, int width, int height)
 {
     if (!g) return PTMI_EINVAL;

@@ -277,6 +277,23 @@ hipError_t launch_mesh_build_order(const float *triangles, int n, int n_kept, co
                                    int32_t *order, hipStream_t stream);
 hipError_t launch_mesh_build_scatter(const float *triangles, int n, int n_kept, const int32_t *leaf_pos, float4 *by_index, float4 *geom, float4 *materials,
                                      hipStream_t stream);
+// The builds' radix sort (ptmi_mesh_build.hip; the mesh build and the sphere build call it): n (key, index) pairs in `scratch`
+// (mesh_build_sort_bytes(n) bytes: two key arrays, two index arrays, the tiles' digit counts; the pairs to sort in the first of each),
+// ascending by key -- bits 0 .. 47 -- equal keys in their order.  *sorted: where the sorted indices lie afterwards (within scratch).
+inline uint64_t *sort_keys(void *scratch, int) { return static_cast<uint64_t *>(scratch); }
+inline uint32_t *sort_indices(void *scratch, int n) { return reinterpret_cast<uint32_t *>(static_cast<uint64_t *>(scratch) + 2 * (size_t)n); }
+hipError_t launch_sort_pairs(void *scratch, int n, const uint32_t **sorted, hipStream_t stream);
+// Moving or replacing the spheres of a BVH or mesh scene (ptmi_update_spheres, ptmi_set_bvh_spheres; ptmi_bvh_refit.hip).  spheres: n records
+// of `words` floats by original index, device memory: 4 -- (x, y, z, radius) -- or 10 -- a ptmi_sphere.  check writes `result` only
+// (kSphWords words, ptmi_bvh_box.h: all ones in [0, kSphHi), zero behind, at launch).  records: (c, r * r) into `geom` in leaf order and
+// into the scene block's sphere rows, and with 10 words the material pairs (`materials`: the pair of sphere 0).  level: the boxes and
+// inv_2r of `count` nodes whose children are complete (one launch per level of BvhLevelPlan, the deepest first).
+hipError_t launch_bvh_check(const float *spheres, int words, int n, unsigned int *result, hipStream_t stream);
+hipError_t launch_bvh_records(const float *spheres, int words, int n, const int32_t *order, float4 *geom, float4 *scene, float4 *materials, hipStream_t stream);
+hipError_t launch_bvh_level(float4 *nodes, const float *spheres, int words, int n, const int32_t *order, const int32_t *level_nodes, int count, hipStream_t stream);
+// The leaf order of ptmi_set_bvh_spheres (ptmi_bvh_build.hip): the Morton keys of the centres within lo / hi (the box check found), the
+// sort above (scratch: mesh_build_sort_bytes(n) bytes), then order[position] = original index.
+hipError_t launch_bvh_build_order(const float *spheres, int n, const float lo[3], const float hi[3], void *scratch, int32_t *order, hipStream_t stream);
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

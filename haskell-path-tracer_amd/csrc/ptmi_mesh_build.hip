@@ -275,18 +275,16 @@ size_t mesh_build_sort_bytes(int n)
     return 2 * m * sizeof(uint64_t) + 2 * m * sizeof(uint32_t) + tiles * kDigits * sizeof(unsigned int);
 }
 
-hipError_t launch_mesh_build_order(const float *triangles, int n, int n_kept, const float lo[3], const float hi[3], void *scratch, int32_t *leaf_pos,
-                                   int32_t *order, hipStream_t stream)
+// The radix sort of n (key, index) pairs that lie in `scratch` (sort_keys / sort_indices of ptmi_kernels.h; mesh_build_sort_bytes(n)
+// bytes), ascending by key, equal keys in their order: six passes over bits 0 .. 47.  *sorted: where the sorted indices are afterwards.
+hipError_t launch_sort_pairs(void *scratch, int n, const uint32_t **sorted, hipStream_t stream)
 {
-    if (n <= 0) return hipSuccess;
     const size_t m = (size_t)n;
     const int tiles = (int)((m + kSortTile - 1) / kSortTile);
-    uint64_t *keys[2] = {static_cast<uint64_t *>(scratch), static_cast<uint64_t *>(scratch) + m};
-    uint32_t *indices[2] = {reinterpret_cast<uint32_t *>(keys[1] + m), reinterpret_cast<uint32_t *>(keys[1] + m) + m};
+    uint64_t *keys[2] = {sort_keys(scratch, n), sort_keys(scratch, n) + m};
+    uint32_t *indices[2] = {sort_indices(scratch, n), sort_indices(scratch, n) + m};
     unsigned int *counts = indices[1] + m;
-    MortonBox box;
-    for (int a = 0; a < 3; ++a) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    hipError_t e = launch(mesh_build_keys_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, triangles, n, box, keys[0], indices[0], aligned(triangles));
+    hipError_t e = hipSuccess;
     int from = 0;
     for (int shift = 0; shift <= kMortonKeyBits && e == hipSuccess; shift += 8, from ^= 1) {      // six passes: bits 0 .. 47
         e = launch(mesh_build_sort_histogram_kernel, dim3(tiles), dim3(kBlock), 0, stream, keys[from], n, shift, counts);
@@ -294,7 +292,21 @@ hipError_t launch_mesh_build_order(const float *triangles, int n, int n_kept, co
         if (e == hipSuccess)
             e = launch(mesh_build_sort_scatter_kernel, dim3(tiles), dim3(kBlock), 0, stream, keys[from], indices[from], n, shift, counts, keys[from ^ 1], indices[from ^ 1]);
     }
-    if (e == hipSuccess) e = launch(mesh_build_order_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, indices[from], n, n_kept, leaf_pos, order);
+    *sorted = indices[from];
+    return e;
+}
+
+hipError_t launch_mesh_build_order(const float *triangles, int n, int n_kept, const float lo[3], const float hi[3], void *scratch, int32_t *leaf_pos,
+                                   int32_t *order, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    MortonBox box;
+    for (int a = 0; a < 3; ++a) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    hipError_t e = launch(mesh_build_keys_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, triangles, n, box, sort_keys(scratch, n), sort_indices(scratch, n),
+                          aligned(triangles));
+    const uint32_t *sorted = nullptr;
+    if (e == hipSuccess) e = launch_sort_pairs(scratch, n, &sorted, stream);
+    if (e == hipSuccess) e = launch(mesh_build_order_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, sorted, n, n_kept, leaf_pos, order);
     return e;
 }
 

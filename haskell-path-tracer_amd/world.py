@@ -200,6 +200,36 @@ def displaced(v, amount, kind="wave", centre=(1.0, 3.0, -16.0), radius=3.0, seed
     return np.ascontiguousarray(out.astype(np.float32).reshape(a.shape))
 
 
+def sphere_geometry(spheres):
+    """The geometry of SPHERE_DTYPE records as Context.update_spheres takes it -> (n, 4) float32, [k] = (x, y, z, radius)"""
+    s = np.asarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    return np.ascontiguousarray(np.concatenate([s["position"], s["radius"][:, None]], axis=1), dtype=np.float32).reshape(-1, 4)
+
+
+def with_sphere_geometry(spheres, g):
+    """A copy of the spheres with the geometry g ((n, 4), as sphere_geometry gives it); materials kept"""
+    s = np.array(spheres, dtype=SPHERE_DTYPE, copy=True).reshape(-1)
+    g = np.asarray(g, np.float32).reshape(len(s), 4)
+    s["position"], s["radius"] = g[:, :3], g[:, 3]
+    return s
+
+
+def displaced_spheres(g, amount, kind="wave", seed=0):
+    """Sphere geometry (as sphere_geometry gives it) with every centre moved by up to `amount` (a length), radii kept: kind "wave" a
+    smooth wave along y over x and z, kind "noise" an independent seeded offset per sphere and axis.  -> (n, 4) float32; tests and
+    tools/bvh_update_bench.py"""
+    out = np.array(g, np.float32, copy=True).reshape(-1, 4)
+    p = out[:, :3].astype(np.float64)
+    if kind == "wave":
+        p[:, 1] += amount * np.sin(0.7 * p[:, 0] + 0.9 * seed) * np.cos(0.5 * p[:, 2])
+    elif kind == "noise":
+        p += amount * (2.0 * np.random.default_rng(seed).random(p.shape) - 1.0)
+    else:
+        raise ValueError("kind is 'wave' or 'noise'")
+    out[:, :3] = p.astype(np.float32)
+    return np.ascontiguousarray(out)
+
+
 def load_obj(path_or_text, material):
     """A minimal Wavefront OBJ reader: `v x y z` and `f a b c ...` lines only (1-based indices, negative ones counted back from the
     last vertex read, `a/b/c` forms use the position index); polygons are fan-triangulated (a b c, a c d, ...); every other line is

@@ -46,7 +46,10 @@ extern "C" {
                             * vertices (ptmi_update_mesh_vertices, ptmi_update_mesh_vertices_device, ptmi_group_update_mesh_vertices,
                             * ptmi_mesh_refit_layout, ptmi_mesh_read_layout); new triangles for a mesh scene, built on the device
                             * (ptmi_set_mesh_triangles, ptmi_set_mesh_triangles_device, ptmi_group_set_mesh_triangles,
-                            * ptmi_mesh_layout_morton). */
+                            * ptmi_mesh_layout_morton); moving and replacing a BVH or mesh scene's spheres on the device
+                            * (ptmi_update_spheres, ptmi_update_spheres_device, ptmi_set_bvh_spheres, ptmi_set_bvh_spheres_device,
+                            * ptmi_group_update_spheres, ptmi_group_set_bvh_spheres, ptmi_bvh_refit_layout, ptmi_bvh_layout_morton,
+                            * ptmi_bvh_read_layout). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -240,7 +243,8 @@ int ptmi_mesh_layout(const ptmi_triangle *triangles, int n_triangles, ptmi_bvh_n
  * The topology is the one built for the scene AS SET: after large deformations the refitted boxes overlap more than a fresh build's
  * and renders get slower, never different (DESIGN.md 5.8 has the measurements); call ptmi_set_scene_mesh again then, or
  * ptmi_set_mesh_triangles[_device] when the triangles live on the device or their count or connectivity changes.  Moving
- * spheres or planes, or changing materials, is a scene call. */
+ * or replacing the spheres is ptmi_update_spheres / ptmi_set_bvh_spheres (below); moving planes, or changing the materials of planes
+ * or triangles, is a scene call. */
 int ptmi_update_mesh_vertices(ptmi_ctx *ctx, const float *vertices, int n_triangles);          /* host memory   */
 int ptmi_update_mesh_vertices_device(ptmi_ctx *ctx, const float *d_vertices, int n_triangles); /* device memory */
 
@@ -293,6 +297,70 @@ int ptmi_mesh_layout_morton(const ptmi_triangle *triangles, int n_triangles, ptm
  * NULL nothing is copied: the return value and *n_kept say what to allocate.  Returns the number of nodes; PTMI_ESTATE when the
  * current scene is not a mesh scene.  Synchronises the context's stream. */
 int ptmi_mesh_read_layout(ptmi_ctx *ctx, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept);
+
+/* MOVE the spheres of the current BVH or MESH scene (both keep them in one sphere hierarchy) and refit that hierarchy on the device, without a
+ * scene call.  geometry: 4 floats per sphere -- x, y, z, radius -- in the index order of the scene as set, in host memory
+ * (ptmi_update_spheres: staged to the device, then the same path) or in device memory of the context's device (ptmi_update_spheres_device;
+ * read on the context's stream).  The count, the materials, the planes and the triangles stay; so do the hierarchy's topology and leaf order.
+ *   - Every later render (all seven planes, Inline and Streams, both seed rules, the GLASS tree walk) and every ptmi_eval_check_hit result
+ *     equals, bit for bit, that of a context given ptmi_set_scene_bvh / ptmi_set_scene_mesh with the moved spheres: the device writes each
+ *     (centre, radius * radius) record by the scene calls' own operation, and check_hit returns the fold over ALL spheres whatever
+ *     hierarchy bounds them.  The refitted boxes and inv_2r are those of ptmi_bvh_refit_layout, bit for bit.
+ *   - A failed update leaves the scene as it was: PTMI_ESTATE for a linear or unset scene; PTMI_EINVAL for a NULL pointer with
+ *     n_spheres > 0, for an n_spheres other than the scene's, and for a non-finite position, radius or radius^2 (ptmi_last_error names the
+ *     smallest offending index).  Validation is a kernel that writes nothing of the scene; the update is written into second copies of the
+ *     hierarchy and scene blocks that replace the first only when every launch is out: after PTMI_EHIP / PTMI_ENOMEM the scene is the one
+ *     before the call.
+ *   - ONE host synchronisation per update (the verdict and the box of the centres, read together); the writing kernels run behind it on
+ *     the context's stream.
+ * The topology is not rebuilt: after large displacements the boxes overlap more and renders get slower, never different; call
+ * ptmi_set_bvh_spheres[_device] or the scene call again then. */
+int ptmi_update_spheres(ptmi_ctx *ctx, const float *geometry, int n_spheres);          /* host memory   */
+int ptmi_update_spheres_device(ptmi_ctx *ctx, const float *d_geometry, int n_spheres); /* device memory */
+
+/* REPLACE the spheres of the current BVH or MESH scene -- another count (0 .. PTMI_MAX_BVH_SPHERES), new materials -- and build their
+ * hierarchy on the device.  spheres: full ptmi_sphere records in host memory (ptmi_set_bvh_spheres: staged, then the same path) or in
+ * device memory (ptmi_set_bvh_spheres_device; read on the context's stream).  Planes and triangles stay as set.
+ *   - Every later render and ptmi_eval_check_hit result equals, bit for bit, that of a context given ptmi_set_scene_bvh /
+ *     ptmi_set_scene_mesh with the new spheres: the packed scene block is rebuilt on the device for the new count, sphere rows and
+ *     materials by the scene calls' own operations, the planes' and triangles' rows copied to their new offsets.
+ *   - The hierarchy is NOT ptmi_bvh_layout's: the leaf order ascends by (Morton key of the centre within the f32 box of all centres, index)
+ *     -- every sphere is kept, radius 0 too -- the topology is a function of the count alone (equal-count splits, ptmi_bvh_layout's
+ *     depth), the boxes are the refit's over it.  ptmi_bvh_layout_morton is its specification and host twin: ptmi_bvh_read_layout
+ *     afterwards returns exactly its nodes and order.
+ *   - Refusals leave the scene as it was: PTMI_ESTATE for a linear or unset scene; PTMI_ELIMIT beyond the limit; PTMI_EINVAL for a NULL
+ *     pointer with n_spheres > 0, a negative n_spheres, 0 spheres in a scene with nothing else, a non-finite position, radius, radius^2,
+ *     colour, illuminance or brdf_param, or an unknown brdf_tag (the smallest offending index is named).  Validation is a kernel that
+ *     writes nothing of the scene; new blocks are written aside and swapped in only when every launch is out: after PTMI_EHIP /
+ *     PTMI_ENOMEM the scene is the one before the call.  A GLASS sphere under PTMI_SEED_FROM_RESULT is refused where
+ *     ptmi_set_mesh_triangles' GLASS is: by the next render Streams, not here.
+ *   - TWO host synchronisations per call: the verdict, box and GLASS flag; then the drained stream before the old blocks go.
+ * Measured (tools/bvh_update_bench.py, profiles/bvh_update_bench.json; an MI355X at 2.4 GHz), 1 020 / 10^5 / 10^6 spheres, from device
+ * memory: ptmi_update_spheres 0.07 / 0.21 / 0.32 ms (from host memory 0.08 / 0.37 / 0.81), ptmi_set_bvh_spheres 0.19 / 1.98 / 11.2 ms
+ * (host 0.21 / 2.51 / 11.4), ptmi_set_scene_bvh 0.14 / 22.0 / 309 ms.  The Morton order with equal-count splits is another tree than
+ * ptmi_bvh_layout's median splits: a 1080p render over it takes x 1.92 / 3.73 / 6.99 of the time over ptmi_bvh_layout's (the field is
+ * flat, and the key spends 14 bits on every axis whatever its extent); over a tree REFITTED after every sphere moved by up to a tenth
+ * of the field's width it takes x 1.56 / 35.8 / 216.  Refit small motions, rebuild large ones; ptmi_set_scene_bvh remains the call
+ * for a static scene. */
+int ptmi_set_bvh_spheres(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres);          /* host memory   */
+int ptmi_set_bvh_spheres_device(ptmi_ctx *ctx, const ptmi_sphere *d_spheres, int n_spheres); /* device memory */
+
+/* The host twin of ptmi_update_spheres' refit (pure host code, no device): `nodes` (n_nodes of them) and `order` as ptmi_bvh_layout or
+ * ptmi_bvh_layout_morton returned them, `spheres` the moved ones.  Overwrites center, half and inv_2r of every child in place with
+ * ptmi_bvh_layout's own arithmetic (csrc/ptmi_bvh_box.h); `ref` and `order` are not touched.  Unchanged spheres give ptmi_bvh_layout's
+ * nodes back byte for byte, and so does moving away and back.  PTMI_EINVAL, with nothing written, for nodes and order that do not
+ * belong together or non-finite sphere data. */
+int ptmi_bvh_refit_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int n_nodes, const int32_t *order);
+
+/* The hierarchy ptmi_set_bvh_spheres builds, without a device (pure host code, deterministic): ptmi_bvh_layout's signature and return
+ * values; it refuses what ptmi_set_bvh_spheres refuses in a sphere.  ptmi_bvh_refit_layout leaves the result byte-identical. */
+int ptmi_bvh_layout_morton(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
+
+/* The sphere hierarchy the context's BVH or mesh scene holds NOW, copied back from the device (test and diagnostic surface).  `nodes`
+ * needs the scene's node count (node_capacity; PTMI_ELIMIT when too small), `order` its sphere count -- the sum of the leaves' counts
+ * in `nodes` -- or NULL: the nodes alone are copied, which say how long the order is.  With both NULL nothing is copied
+ * and the node count is returned.  Returns the number of nodes; PTMI_ESTATE for a linear or unset scene.  Synchronises the stream. */
+int ptmi_bvh_read_layout(ptmi_ctx *ctx, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
 
 /* screenWidth / screenHeight (src/Util.hs:186-188) as run-time values.  Allocates the
  * seven device planes the context owns (for the rows of its partition, see below) and
@@ -595,6 +663,8 @@ int ptmi_group_set_scene_mesh(ptmi_group *group, const ptmi_sphere *spheres, int
                               const ptmi_plane *planes, int n_planes);   /* ptmi_set_scene_mesh on every member */
 int ptmi_group_update_mesh_vertices(ptmi_group *group, const float *vertices, int n_triangles);   /* ptmi_update_mesh_vertices on every member */
 int ptmi_group_set_mesh_triangles(ptmi_group *group, const ptmi_triangle *triangles, int n_triangles);   /* ptmi_set_mesh_triangles on every member */
+int ptmi_group_update_spheres(ptmi_group *group, const float *geometry, int n_spheres);   /* ptmi_update_spheres on every member */
+int ptmi_group_set_bvh_spheres(ptmi_group *group, const ptmi_sphere *spheres, int n_spheres);   /* ptmi_set_bvh_spheres on every member */
 int ptmi_group_resize(ptmi_group *group, int width, int height);
 int ptmi_group_init_output(ptmi_group *group, uint64_t seed0);
 int ptmi_group_reseed(ptmi_group *group, uint64_t seed0);
