@@ -15,6 +15,8 @@ from .world import CAMERA_DTYPE, PLANE_DTYPE, SPHERE_DTYPE, TRIANGLE_DTYPE, INLI
 
 OPT_STREAMS_SEED_RULE, OPT_STREAM_STEP_CAP, OPT_STREAM_CAPACITY, OPT_STREAMS_FORM, OPT_STREAM_BATCH, OPT_SPP_CHUNKS, OPT_ARITHMETIC = 1, 2, 3, 4, 5, 6, 7
 OPT_STREAM_TAIL, OPT_ORDERED_PASSES, OPT_GLASS_BATCH, OPT_STREAM_GRADED, OPT_SNAPSHOT_BUDGET_MB, OPT_STREAM_PASS_GROUPS, OPT_CHAIN_SLOTS, OPT_PASS_HANDOFF = 8, 9, 10, 11, 12, 13, 14, 15
+OPT_BVH_DEVICE_BUILD = 17                                        # (16 is unused)
+BVH_BUILD_EQUAL_COUNT, BVH_BUILD_SPATIAL = 0, 1
 CHAIN_CONSUME = 1
 HANDOFF_FENCED, HANDOFF_FENCE_FREE = 0, 1
 ARITH_EXACT, ARITH_CONTRACTED = 0, 1
@@ -67,6 +69,7 @@ SYMBOLS = {
     "ptmi_set_bvh_spheres_device": (C.c_int, [_vp, _vp, C.c_int]),
     "ptmi_bvh_refit_layout": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_bvh_layout_morton": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_bvh_layout_spatial": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_bvh_read_layout": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "ptmi_resize": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ptmi_set_partition": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -218,6 +221,18 @@ def bvh_layout_morton(spheres):
     got = load_library().ptmi_bvh_layout_morton(_ptr(s) if s.size else None, s.size, _ptr(nodes), nodes.size, _ptr(order) if s.size else None)
     if got < 0:
         raise PtmiError(got, "ptmi_bvh_layout_morton")
+    return nodes[:got].copy(), order
+
+
+def bvh_layout_spatial(spheres):
+    """ptmi_bvh_layout_spatial: the hierarchy ptmi_set_bvh_spheres builds on the device under OPT_BVH_DEVICE_BUILD = BVH_BUILD_SPATIAL (host
+    code, no device) -> (nodes, order) as bvh_layout returns them."""
+    s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+    nodes = np.zeros(max(1, s.size), BVH_NODE_DTYPE)
+    order = np.zeros(s.size, np.int32)
+    got = load_library().ptmi_bvh_layout_spatial(_ptr(s) if s.size else None, s.size, _ptr(nodes), nodes.size, _ptr(order) if s.size else None)
+    if got < 0:
+        raise PtmiError(got, "ptmi_bvh_layout_spatial")
     return nodes[:got].copy(), order
 
 

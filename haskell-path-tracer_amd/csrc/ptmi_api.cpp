@@ -19,6 +19,7 @@
 
 #include "ptmi_bvh.h"
 #include "ptmi_bvh_box.h"
+#include "ptmi_bvh_spatial.h"
 #include "ptmi_mesh.h"
 #include "ptmi_mesh_box.h"
 #include "ptmi_mesh_morton.h"
@@ -80,6 +81,7 @@ struct ptmi_ctx {
     DeviceBlock d_bvh_shadow, d_scene_shadow, d_bvh_plan, d_sphere_staging;
     size_t bvh_nodes_f4 = 0;                                         // d_bvh: nodes | spheres in leaf order | indices
     std::vector<int32_t> bvh_level_first;
+    int opt_bvh_build = PTMI_BVH_BUILD_EQUAL_COUNT;   // PTMI_OPT_BVH_DEVICE_BUILD: which tree ptmi_set_bvh_spheres builds
     bool planes_have_glass = false, triangles_have_glass = false;    // GLASS among what ptmi_set_bvh_spheres keeps
 
     DeviceBlock d_live;      // unsigned long long
@@ -1848,7 +1850,9 @@ int ptmi_update_spheres(ptmi_ctx *c, const float *geometry, int n_spheres)
 
 // New spheres for the current BVH or mesh scene (see include/ptmi.h).  The check kernel reads the new spheres only; the host reads its
 // verdict, the box of the centres and the GLASS flag back together (the first synchronisation); then fresh blocks -- the scene block for
-// the new count, the hierarchy, its plan -- are filled on the stream and become the scene's when all of it is through (the second).  c->mu is held.
+// the new count, the hierarchy, its plan -- are filled on the stream and become the scene's when all of it is through (the second).  Under
+// PTMI_BVH_BUILD_SPATIAL the topology is built on the device first and the counts of its levels are read back (one synchronisation more,
+// three in all).  c->mu is held.
 static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
 {
     unsigned int *result = c->d_bvh_plan.as<unsigned int>();
@@ -1869,19 +1873,51 @@ static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     if (n > 0)
         for (int a = 0; a < 3; ++a) { lo[a] = ordered_value(got[kSphLo + a]); hi[a] = ordered_value(got[kSphHi + a]); }
-    // the topology and its levels are functions of the count alone (ptmi_mesh_morton.h)
+    const size_t old_ns = (size_t)c->n_spheres, np = (size_t)c->n_planes, nt = c->scene_mesh ? (size_t)c->mesh.n_triangles : 0, ns = (size_t)n;
+    const bool spatial = c->opt_bvh_build == PTMI_BVH_BUILD_SPATIAL;
     std::vector<ptmi_bvh_node> topology;
     BvhLevelPlan plan;
-    morton_topology(n, topology);
-    bvh_level_plan(topology, plan);
-    const size_t old_ns = (size_t)c->n_spheres, np = (size_t)c->n_planes, nt = c->scene_mesh ? (size_t)c->mesh.n_triangles : 0, ns = (size_t)n;
-    const size_t nodes_f4 = topology.size() * 4;
-    DeviceBlock fresh, fresh_bvh, fresh_plan, sort;
-    auto undo = [&]() { release(fresh); release(fresh_bvh); release(fresh_plan); release(sort); };
-    hipError_t e = allocate(fresh, (ns + 2 * np + 2 * (ns + np) + 2 * nt) * sizeof(float4));
+    DeviceBlock fresh, fresh_bvh, fresh_plan, sort, work;
+    auto undo = [&]() { release(fresh); release(fresh_bvh); release(fresh_plan); release(sort); release(work); };
+    hipError_t e = hipSuccess;
+    size_t n_nodes = 0;
+    const uint32_t *sorted = nullptr;
+    int level_count[kSpatialWords] = {0};
+    int levels = 0;
+    if (!spatial) {
+        // the topology and its levels are functions of the count alone (ptmi_mesh_morton.h)
+        morton_topology(n, topology);
+        bvh_level_plan(topology, plan);
+        n_nodes = topology.size();
+    } else {
+        // the topology is the keys' (ptmi_bvh_spatial.h): built level by level into scratch, and the levels' counts read back -- this
+        // build's extra synchronisation -- before the hierarchy can be allocated
+        if (n > 0) e = allocate(sort, mesh_build_sort_bytes(n));
+        if (e == hipSuccess) e = allocate(work, bvh_spatial_work_bytes(n));
+        if (e == hipSuccess) e = launch_bvh_spatial_tree(d_spheres, n, lo, hi, sort.p, work.p, &sorted, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(level_count, bvh_spatial_report(work.p, n), sizeof level_count, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t read = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = read;
+        if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
+        // levels of 1, <= 2, <= 4 ... nodes, then none: anything else is not a tree this build makes
+        bool sane = level_count[0] == 1;
+        for (levels = 0; levels < PTMI_BVH_MAX_DEPTH && level_count[levels] > 0; ++levels) {
+            sane = sane && level_count[levels] <= spatial_level_bound(n, levels) && (levels == 0 || level_count[levels] <= 2 * level_count[levels - 1]);
+            n_nodes += (size_t)level_count[levels];
+        }
+        for (int l = levels; l < PTMI_BVH_MAX_DEPTH; ++l) sane = sane && level_count[l] == 0;
+        if (!sane || n_nodes > (size_t)spatial_node_bound(n)) {
+            undo();
+            return fail(c, PTMI_EHIP, "the device build of the sphere hierarchy reported levels that are no tree");
+        }
+        plan.level_first.assign(1, 0);
+        for (int l = levels - 1; l >= 0; --l) plan.level_first.push_back(plan.level_first.back() + level_count[l]);      // the deepest first
+    }
+    const size_t nodes_f4 = n_nodes * 4;
+    e = allocate(fresh, (ns + 2 * np + 2 * (ns + np) + 2 * nt) * sizeof(float4));
     if (e == hipSuccess) e = allocate(fresh_bvh, (nodes_f4 + ns + (ns + 3) / 4) * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_plan, kBvhPlanLevelsAt + plan.level_nodes.size() * sizeof(int32_t));
-    if (e == hipSuccess && n > 0) e = allocate(sort, mesh_build_sort_bytes(n));
+    if (e == hipSuccess) e = allocate(fresh_plan, kBvhPlanLevelsAt + n_nodes * sizeof(int32_t));
+    if (e == hipSuccess && n > 0 && !spatial) e = allocate(sort, mesh_build_sort_bytes(n));
     if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
     float4 *scene = fresh.as<float4>(), *nodes = fresh_bvh.as<float4>(), *geom = nodes + nodes_f4;
     const float4 *old_scene = c->d_scene.as<float4>();
@@ -1891,11 +1927,16 @@ static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
     if (np > 0) e = hipMemcpyAsync(scene + ns, old_scene + old_ns, 2 * np * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess && np + nt > 0)
         e = hipMemcpyAsync(scene + ns + 2 * np + 2 * ns, old_scene + old_ns + 2 * np + 2 * old_ns, 2 * (np + nt) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) {
-        CopySpan spans[2] = {{nodes, topology.data(), topology.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
-        e = copy_to_device(c, spans, 2);
+    if (!spatial) {
+        if (e == hipSuccess) {
+            CopySpan spans[2] = {{nodes, topology.data(), topology.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
+            e = copy_to_device(c, spans, 2);
+        }
+        if (e == hipSuccess) e = launch_bvh_build_order(d_spheres, n, lo, hi, sort.p, order, c->stream);
+    } else {
+        if (e == hipSuccess) e = launch_bvh_spatial_finish(work.p, n, level_count, levels, nodes, level_nodes, c->stream);
+        if (e == hipSuccess && n > 0) e = hipMemcpyAsync(order, sorted, ns * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);      // order[position] = original index
     }
-    if (e == hipSuccess) e = launch_bvh_build_order(d_spheres, n, lo, hi, sort.p, order, c->stream);
     if (e == hipSuccess) e = launch_bvh_records(d_spheres, 10, n, order, geom, scene, scene + ns + 2 * np, c->stream);
     for (size_t lv = 0; lv + 1 < plan.level_first.size() && e == hipSuccess; ++lv)
         e = launch_bvh_level(nodes, d_spheres, 10, n, order, level_nodes + plan.level_first[lv], plan.level_first[lv + 1] - plan.level_first[lv], c->stream);
@@ -1905,6 +1946,7 @@ static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
     if (e == hipSuccess) e = drained;
     if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
     release(sort);
+    release(work);
     release(c->d_scene);
     release(c->d_bvh);
     release(c->d_bvh_shadow);
@@ -2183,6 +2225,9 @@ int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
     case PTMI_OPT_PASS_HANDOFF:
         if (value != PTMI_HANDOFF_FENCED && value != PTMI_HANDOFF_FENCE_FREE) return fail(c, PTMI_EINVAL, "unknown pass hand-off");
         c->opt_pass_handoff = (int)value; return PTMI_OK;
+    case PTMI_OPT_BVH_DEVICE_BUILD:
+        if (value != PTMI_BVH_BUILD_EQUAL_COUNT && value != PTMI_BVH_BUILD_SPATIAL) return fail(c, PTMI_EINVAL, "unknown device build of the sphere hierarchy");
+        c->opt_bvh_build = (int)value; return PTMI_OK;
     default: return fail(c, PTMI_EINVAL, "unknown option");
     }
 }
@@ -2208,6 +2253,7 @@ int ptmi_get_option(ptmi_ctx *c, int option, int64_t *value)
     case PTMI_OPT_SNAPSHOT_BUDGET_MB: *value = c->opt_snapshot_mb; return PTMI_OK;
     case PTMI_OPT_CHAIN_SLOTS: *value = c->opt_chain_slots; return PTMI_OK;
     case PTMI_OPT_PASS_HANDOFF: *value = c->opt_pass_handoff; return PTMI_OK;
+    case PTMI_OPT_BVH_DEVICE_BUILD: *value = c->opt_bvh_build; return PTMI_OK;
     default: return fail(c, PTMI_EINVAL, "unknown option");
     }
 }

@@ -15,6 +15,7 @@
 //     adds per ray (check_hit_bvh), using the smallest radius under each child (ptmi_bvh_node.inv_2r).
 #include "ptmi_bvh.h"
 #include "ptmi_bvh_box.h"
+#include "ptmi_bvh_spatial.h"
 #include "ptmi_mesh_morton.h"
 
 #include <algorithm>
@@ -213,7 +214,8 @@ int bvh_refit(const ptmi_sphere *spheres, int n, ptmi_bvh_node *nodes, int n_nod
 
 // ptmi_bvh_layout_morton / the specification of ptmi_set_bvh_spheres: bvh_build's and the scene calls' refusals; the leaf order by
 // (Morton key of the centre, index) and the topology of the count (ptmi_mesh_morton.h); the boxes by the refit over that topology.
-int bvh_build_morton(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why)
+// what both device builds refuse, and the box of the centres
+static int device_build_front(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why)
 {
     auto refuse = [&](int code, const std::string &msg) { if (why) *why = msg; return code; };
     if (n < 0 || (n > 0 && !spheres)) return refuse(PTMI_EINVAL, "bad sphere arguments");
@@ -233,6 +235,12 @@ int bvh_build_morton(const ptmi_sphere *spheres, int n, BvhBuild &out, std::stri
         for (int i = 0; i < n; ++i)
             for (int a = 0; a < 3; ++a) { out.lo[a] = std::min(out.lo[a], spheres[i].position[a]); out.hi[a] = std::max(out.hi[a], spheres[i].position[a]); }
     }
+    return PTMI_OK;
+}
+
+int bvh_build_morton(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why)
+{
+    if (int rc = device_build_front(spheres, n, out, why)) return rc;
     std::vector<uint64_t> key((size_t)n, 0);
     for (int i = 0; i < n; ++i) key[(size_t)i] = morton_key(spheres[i].position, spheres[i].position, spheres[i].position, out.lo, out.hi);
     out.order.resize((size_t)n);
@@ -240,6 +248,51 @@ int bvh_build_morton(const ptmi_sphere *spheres, int n, BvhBuild &out, std::stri
     const uint64_t *kp = key.data();
     std::sort(out.order.begin(), out.order.end(), [kp](int32_t x, int32_t y) { return kp[x] < kp[y] || (kp[x] == kp[y] && x < y); });
     morton_topology(n, out.nodes);
+    return bvh_refit(spheres, n, out.nodes.data(), (int)out.nodes.size(), out.order.data(), why);
+}
+
+// ptmi_bvh_layout_spatial / the specification of ptmi_set_bvh_spheres under PTMI_BVH_BUILD_SPATIAL (ptmi_bvh_spatial.h): the same
+// refusals; the leaf order by (key in cubic cells, index); spatial splits with the depth guard, numbered breadth-first; the refit's boxes.
+int bvh_build_spatial(const ptmi_sphere *spheres, int n, BvhBuild &out, std::string *why, int *fallbacks)
+{
+    if (int rc = device_build_front(spheres, n, out, why)) return rc;
+    const double den = spatial_den(out.lo, out.hi);
+    std::vector<uint64_t> key((size_t)n, 0);
+    for (int i = 0; i < n; ++i) key[(size_t)i] = spatial_key(spheres[i].position, out.lo, den);
+    out.order.resize((size_t)n);
+    std::iota(out.order.begin(), out.order.end(), 0);
+    const uint64_t *kp = key.data();
+    std::sort(out.order.begin(), out.order.end(), [kp](int32_t x, int32_t y) { return kp[x] < kp[y] || (kp[x] == kp[y] && x < y); });
+    std::vector<uint64_t> sorted((size_t)n, 0);
+    for (int k = 0; k < n; ++k) sorted[(size_t)k] = key[(size_t)out.order[(size_t)k]];
+    struct Range { int b, e; };
+    std::vector<Range> level{{0, n}}, next;
+    out.nodes.assign(1, ptmi_bvh_node{});
+    int taken = 0;
+    for (int lv = 0, first = 0; !level.empty(); ++lv, first += (int)level.size(), level.swap(next)) {
+        next.clear();
+        const int next_first = first + (int)level.size();
+        for (size_t k = 0; k < level.size(); ++k) {
+            const int b = level[k].b, e = level[k].e;
+            int fell = 0;
+            const int m = e - b > PTMI_BVH_LEAF_MAX ? spatial_split(sorted.data(), b, e, lv, &fell) : e;   // (a small root: all in child 0)
+            taken += fell;
+            const Range child[2] = {{b, m}, {m, e}};
+            int32_t ref[2];
+            for (int c = 0; c < 2; ++c) {
+                if (child[c].e - child[c].b > PTMI_BVH_LEAF_MAX) {
+                    ref[c] = next_first + (int32_t)next.size();
+                    next.push_back(child[c]);
+                } else {
+                    ref[c] = spatial_leaf_ref(child[c].b, child[c].e);
+                }
+            }
+            out.nodes[(size_t)first + k].ref[0] = ref[0];
+            out.nodes[(size_t)first + k].ref[1] = ref[1];
+        }
+        out.nodes.resize((size_t)next_first + next.size(), ptmi_bvh_node{});
+    }
+    if (fallbacks) *fallbacks = taken;
     return bvh_refit(spheres, n, out.nodes.data(), (int)out.nodes.size(), out.order.data(), why);
 }
 
@@ -263,6 +316,18 @@ extern "C" int ptmi_bvh_layout_morton(const ptmi_sphere *spheres, int n_spheres,
     if (n_spheres > PTMI_MAX_BVH_SPHERES) return PTMI_ELIMIT;
     ptmi::BvhBuild b;
     if (int rc = ptmi::bvh_build_morton(spheres, n_spheres, b, nullptr)) return rc;
+    if (node_capacity < 0 || (size_t)node_capacity < b.nodes.size()) return PTMI_ELIMIT;
+    std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(ptmi_bvh_node));
+    if (n_spheres > 0) std::memcpy(order, b.order.data(), (size_t)n_spheres * sizeof(int32_t));
+    return (int)b.nodes.size();
+}
+
+extern "C" int ptmi_bvh_layout_spatial(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order)
+{
+    if (n_spheres < 0 || !nodes || (n_spheres > 0 && (!spheres || !order))) return PTMI_EINVAL;
+    if (n_spheres > PTMI_MAX_BVH_SPHERES) return PTMI_ELIMIT;
+    ptmi::BvhBuild b;
+    if (int rc = ptmi::bvh_build_spatial(spheres, n_spheres, b, nullptr, nullptr)) return rc;
     if (node_capacity < 0 || (size_t)node_capacity < b.nodes.size()) return PTMI_ELIMIT;
     std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(ptmi_bvh_node));
     if (n_spheres > 0) std::memcpy(order, b.order.data(), (size_t)n_spheres * sizeof(int32_t));

@@ -24,6 +24,10 @@ const char *bvh_sphere_refusal(const ptmi_sphere &sphere);   // why no box can b
 // (ptmi_mesh_morton.h), the topology a function of the count, bvh_refit's boxes; it also refuses what the scene calls refuse in a
 // sphere's material.
 int bvh_build_morton(const ptmi_sphere *spheres, int n_spheres, BvhBuild &out, std::string *why);
+// ... and for ptmi_bvh_layout_spatial, the twin of the spatial device build (PTMI_BVH_BUILD_SPATIAL; ptmi_bvh_spatial.h): the same refusals,
+// keys in cubic cells, splits at the highest differing key bit within the depth limit, nodes numbered breadth-first.  *fallbacks (may be
+// NULL): how many nodes took the equal-count split.
+int bvh_build_spatial(const ptmi_sphere *spheres, int n_spheres, BvhBuild &out, std::string *why, int *fallbacks);
 
 // What the device refit (ptmi_update_spheres, ptmi_bvh_refit.hip) needs of a hierarchy besides the hierarchy itself.
 struct BvhLevelPlan {

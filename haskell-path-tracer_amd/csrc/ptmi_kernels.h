@@ -294,6 +294,16 @@ hipError_t launch_bvh_level(float4 *nodes, const float *spheres, int words, int 
 // The leaf order of ptmi_set_bvh_spheres (ptmi_bvh_build.hip): the Morton keys of the centres within lo / hi (the box check found), the
 // sort above (scratch: mesh_build_sort_bytes(n) bytes), then order[position] = original index.
 hipError_t launch_bvh_build_order(const float *spheres, int n, const float lo[3], const float hi[3], void *scratch, int32_t *order, hipStream_t stream);
+// The spatial build of ptmi_set_bvh_spheres (PTMI_BVH_BUILD_SPATIAL; ptmi_bvh_lbvh.hip, ptmi_bvh_spatial.h).  tree: the keys in cubic cells, the
+// sort above (scratch: mesh_build_sort_bytes(n) bytes; *sorted: the leaf order, within scratch), then two launches per level into `work`
+// (bvh_spatial_work_bytes(n) bytes), whose report -- kSpatialWords ints at bvh_spatial_report: the levels' node counts, the equal-count
+// splits taken -- the host reads.  finish: with those counts (`levels` of them, every one positive), the references into `nodes` and the
+// nodes by level, the deepest first, into level_nodes.
+size_t bvh_spatial_work_bytes(int n);
+const int *bvh_spatial_report(void *work, int n);
+hipError_t launch_bvh_spatial_tree(const float *spheres, int n, const float lo[3], const float hi[3], void *scratch, void *work, const uint32_t **sorted,
+                                   hipStream_t stream);
+hipError_t launch_bvh_spatial_finish(void *work, int n, const int *level_count, int levels, float4 *nodes, int32_t *level_nodes, hipStream_t stream);
 unsigned int tree_workgroups(int width, int rows_local);   // workgroups per copy of its grid (RenderArgs.tree_stack holds kTreeFastLevels x 64 records of 64 B for each)
 // 8x8 tiles leave lanes idle on the right and bottom edges; rows of 64 leave them idle at the end only
 inline bool tiles_pay_dims(int width, int rows_local) { return width >= 64 && rows_local >= 16; }

@@ -49,7 +49,8 @@ extern "C" {
                             * ptmi_mesh_layout_morton); moving and replacing a BVH or mesh scene's spheres on the device
                             * (ptmi_update_spheres, ptmi_update_spheres_device, ptmi_set_bvh_spheres, ptmi_set_bvh_spheres_device,
                             * ptmi_group_update_spheres, ptmi_group_set_bvh_spheres, ptmi_bvh_refit_layout, ptmi_bvh_layout_morton,
-                            * ptmi_bvh_read_layout). */
+                            * ptmi_bvh_read_layout); the spatial device build of a sphere hierarchy (option 17 = PTMI_OPT_BVH_DEVICE_BUILD,
+                            * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -335,13 +336,24 @@ int ptmi_update_spheres_device(ptmi_ctx *ctx, const float *d_geometry, int n_sph
  *     PTMI_ENOMEM the scene is the one before the call.  A GLASS sphere under PTMI_SEED_FROM_RESULT is refused where
  *     ptmi_set_mesh_triangles' GLASS is: by the next render Streams, not here.
  *   - TWO host synchronisations per call: the verdict, box and GLASS flag; then the drained stream before the old blocks go.
+ *   - Under PTMI_OPT_BVH_DEVICE_BUILD = PTMI_BVH_BUILD_SPATIAL everything above holds but the tree: it is ptmi_bvh_layout_spatial's, bit for
+ *     bit, built on the device top-down, two launches per level, its nodes numbered breadth-first by a prefix sum in id order (no atomics).
+ *     The host reads 25 words back in between -- the node count of every level, which size the hierarchy, the refit's launches and a later
+ *     ptmi_update_spheres -- so the call makes THREE host synchronisations.
  * Measured (tools/bvh_update_bench.py, profiles/bvh_update_bench.json; an MI355X at 2.4 GHz), 1 020 / 10^5 / 10^6 spheres, from device
  * memory: ptmi_update_spheres 0.07 / 0.21 / 0.32 ms (from host memory 0.08 / 0.37 / 0.81), ptmi_set_bvh_spheres 0.19 / 1.98 / 11.2 ms
  * (host 0.21 / 2.51 / 11.4), ptmi_set_scene_bvh 0.14 / 22.0 / 309 ms.  The Morton order with equal-count splits is another tree than
  * ptmi_bvh_layout's median splits: a 1080p render over it takes x 1.92 / 3.73 / 6.99 of the time over ptmi_bvh_layout's (the field is
  * flat, and the key spends 14 bits on every axis whatever its extent); over a tree REFITTED after every sphere moved by up to a tenth
  * of the field's width it takes x 1.56 / 35.8 / 216.  Refit small motions, rebuild large ones; ptmi_set_scene_bvh remains the call
- * for a static scene. */
+ * for a static scene.
+ * Under PTMI_BVH_BUILD_SPATIAL (the same tool, profiles/bvh_spatial_bench.json; another MI355X, on which bench.py implied 2.42 GHz; every
+ * figure against the other builder and the host's tree in the SAME session), 1 020 / 10^5 / 10^6 spheres: the 1080p render over the
+ * spatial tree takes x 1.005 / 1.021 / 0.988 of the time over ptmi_bvh_layout's (over the equal-count tree there: x 1.92 / 3.72 / 7.05);
+ * the call takes 0.39 / 1.35 / 2.12 ms from device memory (from host memory 0.41 / 1.54 / 3.05), against 0.19 / 2.60 / 6.16 (0.21 / 2.79 /
+ * 7.16) for the equal-count build there -- its 48 small launches and third synchronisation cost the small scene 0.2 ms, and it uploads no
+ * topology.  The trees have 12 / 20 / 23 levels of inner nodes and 357 / 35 437 / 354 454 nodes; no node of them fell back to the
+ * equal-count split. */
 int ptmi_set_bvh_spheres(ptmi_ctx *ctx, const ptmi_sphere *spheres, int n_spheres);          /* host memory   */
 int ptmi_set_bvh_spheres_device(ptmi_ctx *ctx, const ptmi_sphere *d_spheres, int n_spheres); /* device memory */
 
@@ -355,6 +367,15 @@ int ptmi_bvh_refit_layout(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_no
 /* The hierarchy ptmi_set_bvh_spheres builds, without a device (pure host code, deterministic): ptmi_bvh_layout's signature and return
  * values; it refuses what ptmi_set_bvh_spheres refuses in a sphere.  ptmi_bvh_refit_layout leaves the result byte-identical. */
 int ptmi_bvh_layout_morton(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
+
+/* The hierarchy ptmi_set_bvh_spheres builds under PTMI_BVH_BUILD_SPATIAL, without a device: ptmi_bvh_layout_morton's signature, return values
+ * and refusals.  The leaf order ascends by (key, index) with, per axis a, q = min(16383, floor(((c[a] - lo[a]) * 16384) / den)) in f64, den the
+ * LONGEST extent of the f32 box [lo, hi] of all centres (q = 0 when den is 0), interleaved as for ptmi_bvh_layout_morton.  The root is level 0;
+ * a range [b, e) of more than PTMI_BVH_LEAF_MAX spheres at level L splits at the first position m whose key has the highest bit set in which
+ * the range's first and last key differ, if L + 1 + levels(max(m - b, e - m)) <= PTMI_BVH_MAX_DEPTH -- levels(k) the inner levels of
+ * equal-count splits over k spheres -- and at b + (e - b) / 2 otherwise or when all its keys are equal.  Nodes are numbered level by level,
+ * within a level by ascending b; the boxes are ptmi_bvh_refit_layout's, which leaves the result byte-identical. */
+int ptmi_bvh_layout_spatial(const ptmi_sphere *spheres, int n_spheres, ptmi_bvh_node *nodes, int node_capacity, int32_t *order);
 
 /* The sphere hierarchy the context's BVH or mesh scene holds NOW, copied back from the device (test and diagnostic surface).  `nodes`
  * needs the scene's node count (node_capacity; PTMI_ELIMIT when too small), `order` its sphere count -- the sum of the leaves' counts
@@ -498,8 +519,17 @@ enum {
      * loads after the poll, NO fence: the "valid form" of MI355X_MICROARCH.md, MEASURED valid on gfx950 (5 billion hand-offs compared bit for
      * bit, profiles/r05_soak_ordered_passes.json) -- not a promise of the memory model.  Never chosen automatically: with this value
      * PTMI_OPT_ORDERED_PASSES = 0 means one pass. */
-    PTMI_OPT_PASS_HANDOFF = 15
+    PTMI_OPT_PASS_HANDOFF = 15,
+    /* (16 is unused.)  PTMI_OPT_BVH_DEVICE_BUILD: which sphere hierarchy LATER calls of ptmi_set_bvh_spheres[_device] and
+     * ptmi_group_set_bvh_spheres build, on BVH and on mesh scenes; the scene held is not touched, and ptmi_set_scene_bvh, ptmi_set_scene_mesh,
+     * ptmi_update_spheres and the mesh triangle calls do not look at it.
+     * PTMI_BVH_BUILD_EQUAL_COUNT (default): keys scaled per axis, every range split at its middle -- ptmi_bvh_layout_morton's tree.
+     * PTMI_BVH_BUILD_SPATIAL: keys in CUBIC cells (one scale, that of the longest axis of the centres' box), every range split where the
+     * highest differing key bit changes, within PTMI_BVH_MAX_DEPTH (a split that would leave no room for the larger side falls back to the
+     * middle) -- ptmi_bvh_layout_spatial's tree, which renders about as fast as ptmi_bvh_layout's (see ptmi_set_bvh_spheres). */
+    PTMI_OPT_BVH_DEVICE_BUILD = 17
 };
+enum { PTMI_BVH_BUILD_EQUAL_COUNT = 0, PTMI_BVH_BUILD_SPATIAL = 1 };
 enum { PTMI_HANDOFF_FENCED = 0, PTMI_HANDOFF_FENCE_FREE = 1 };
 enum { PTMI_ARITH_EXACT = 0, PTMI_ARITH_CONTRACTED = 1 };
 enum { PTMI_SEED_KEEP_ACCUMULATOR = 0, PTMI_SEED_FROM_RESULT = 1, PTMI_SEED_AUTO = 2 };

@@ -8,9 +8,14 @@ ptmi_set_bvh_spheres (the hierarchy built on the device) against ptmi_set_scene_
   (f) render Inline, 1920 x 1080, 8 samples per pixel, bounce limit 8, over ptmi_bvh_layout's tree (longest-axis median splits);
   (g) the same render over that tree REFITTED after a per-sphere displacement of a tenth of the field's width, against (f') the render
       over ptmi_bvh_layout's tree of the displaced spheres -- the same image, another tree;
-  (h) the same render over the device-built tree (Morton order, equal-count splits), against (f).
+  (h) the same render over the device-built tree (Morton order, equal-count splits), against (f);
+  (d'), (e'), (h') the same three for the SPATIAL device build (PTMI_OPT_BVH_DEVICE_BUILD = PTMI_BVH_BUILD_SPATIAL: cubic cells, splits at
+      the highest differing key bit), in the same session as (d), (e), (h) -- whose builder is the one every earlier version had -- with
+      the spatial tree's depth, node count and the share of its nodes that fell back to the equal-count split (counted by the numpy
+      restatement of tests/bvh_spatial_scenes.py, which the tests hold equal to the device's tree).
 No ratio is a gate: the figures are what they are.
-Usage: tools/bvh_update_bench.py [--reps 5] [--warmup 2] [--spheres 1020,100000,1000000] [--out FILE]  (profiles/bvh_update_bench.json)"""
+Usage: tools/bvh_update_bench.py [--reps 5] [--warmup 2] [--spheres 1020,100000,1000000] [--out FILE]
+(profiles/bvh_update_bench.json: the run before the spatial build existed; profiles/bvh_spatial_bench.json: with it)"""
 import argparse
 import json
 import os
@@ -21,6 +26,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
@@ -94,17 +100,34 @@ def main():
             set_dev_ms = median_of(lambda: (c.set_bvh_spheres(d10), c.synchronize()))
             morton_ms, got = render_ms(c)
             same = same and equal(got, want)
+            c.set_option(B.OPT_BVH_DEVICE_BUILD, B.BVH_BUILD_SPATIAL)
+            spatial_host_ms = median_of(lambda: (c.set_bvh_spheres(s), c.synchronize()))
+            spatial_dev_ms = median_of(lambda: (c.set_bvh_spheres(d10), c.synchronize()))
+            spatial_ms, got = render_ms(c)
+            c.set_option(B.OPT_BVH_DEVICE_BUILD, B.BVH_BUILD_EQUAL_COUNT)
+            same = same and equal(got, want)
+            import bvh_spatial_scenes as spatial
+            _, _, level_first, fallbacks = spatial.restate(s)
+            same = same and c.bvh_read_layout()[0].shape[0] == level_first[-1]
             same_all = same_all and same
             row = {"spheres": int(n), "set_scene_bvh_ms": round(set_ms, 3), "update_spheres_host_ms": round(upd_host_ms, 3),
                    "update_spheres_device_ms": round(upd_dev_ms, 3), "set_bvh_spheres_host_ms": round(set_host_ms, 3),
                    "set_bvh_spheres_device_ms": round(set_dev_ms, 3), "render_ms_host_tree": round(host_tree_ms, 3),
                    "render_ms_host_tree_of_moved": round(moved_tree_ms, 3), "render_ms_refitted_tree": round(refit_ms, 3),
                    "refitted_over_host_tree": round(refit_ms / moved_tree_ms, 3), "render_ms_morton_tree": round(morton_ms, 3),
-                   "morton_over_host_tree": round(morton_ms / host_tree_ms, 3), "images_equal": bool(same)}
+                   "morton_over_host_tree": round(morton_ms / host_tree_ms, 3),
+                   "set_bvh_spheres_spatial_host_ms": round(spatial_host_ms, 3), "set_bvh_spheres_spatial_device_ms": round(spatial_dev_ms, 3),
+                   "render_ms_spatial_tree": round(spatial_ms, 3), "spatial_over_host_tree": round(spatial_ms / host_tree_ms, 3),
+                   "spatial_over_equal_count_call": round(spatial_dev_ms / set_dev_ms, 3),
+                   "spatial_tree_levels": len(level_first) - 1, "spatial_tree_nodes": int(level_first[-1]),
+                   "spatial_fallback_share": round(fallbacks / max(1, level_first[-1]), 6), "images_equal": bool(same)}
             print("%8d spheres: set_scene_bvh %9.3f ms | update_spheres host %8.3f ms, device %8.3f ms | set_bvh_spheres host %8.3f ms, device %8.3f ms | "
                   "render %8.3f ms over the host's tree, refitted x %.3f, Morton x %.3f, images %s" % (
                       n, set_ms, upd_host_ms, upd_dev_ms, set_host_ms, set_dev_ms, host_tree_ms, refit_ms / moved_tree_ms, morton_ms / host_tree_ms,
                       "equal" if same else "DIFFER"), flush=True)
+            print("%8d spheres: spatial build host %8.3f ms, device %8.3f ms (x %.3f of the equal-count build) | render x %.3f of the host's tree | %d levels, "
+                  "%d nodes, %d fell back" % (n, spatial_host_ms, spatial_dev_ms, spatial_dev_ms / set_dev_ms, spatial_ms / host_tree_ms, len(level_first) - 1,
+                                              level_first[-1], fallbacks), flush=True)
             rows.append(row)
             del d4, d10
     res = {"tool": "bvh_update_bench", "build_id": B.load_library().build_id, "shape": [a.width, a.height], "spp": a.spp, "limit": a.limit,
