@@ -135,6 +135,7 @@ SYMBOLS = {
     "ptmi_eval_distance_to_plane": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_check_hit": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
 
 
@@ -689,6 +690,13 @@ class Context:
         s, c = np.empty_like(x), np.empty_like(x)
         self._check(self._lib.ptmi_eval_sincos(self._h, _ptr(x), x.size, _ptr(s), _ptr(c)))
         return s, c
+
+    def eval_quaternion(self, half_angles):
+        """ptmi_eval_quaternion: quaternion_from_half_angles on the device for half angles (n x 3) -> (n x 4: w, x, y, z); rows 64 k .. 64 k + 63 share a wave."""
+        a = np.ascontiguousarray(half_angles, dtype=np.float32).reshape(-1, 3)
+        q = np.empty((a.shape[0], 4), np.float32)
+        self._check(self._lib.ptmi_eval_quaternion(self._h, _ptr(a), a.shape[0], _ptr(q)))
+        return q
 
 
 class Group:

@@ -2703,4 +2703,23 @@ int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *
     return PTMI_OK;
 }
 
+int ptmi_eval_quaternion(ptmi_ctx *c, const float *half_angles, int n, float *q_out)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!half_angles || !q_out))) return fail(c, PTMI_EINVAL, "bad quaternion arguments");
+    if (n == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)n;
+    if (int rc = grow(c, c->scratch, nb * 28, "scratch")) return rc;
+    float *da = c->scratch.as<float>(), *dq = da + nb * 3;
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(da, half_angles, nb * 12, hipMemcpyHostToDevice, c->stream));
+    PTMI_HIP(c, launch_eval_quaternion(da, n, dq, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    PTMI_HIP(c, hipMemcpyAsync(q_out, dq, nb * 16, hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
+}
+
 }  // extern "C"

@@ -103,6 +103,10 @@ __host__ __device__ __noinline__ inline Reduced sincos_reduce_large(uint32_t xi)
 // two on the device for ALL 2^32 binary32 arguments and found them bit-identical after the final
 // rounding to binary32 (profiles/r01_verify_sincos.txt) -- glibc's own FMA build (`__sinf_fma`,
 // the variant x86-64 hosts with FMA dispatch to) is the same kind of contraction.
+// Which form runs where: sincos() -- sincos_t<PTMI_SINCOS_FUSED> -- serves a single argument (eval_sincos_kernel, the host's camera uniforms,
+// the oracle's mirror).  The three half angles of a bounce go through quaternion_from_half_angles, which on the device takes the quadrant
+// by comparison (sincos_quadrant, below) for a whole wave at a time and falls back to three sincos() calls when any lane's angle is outside
+// that form's range.
 // An FMA with two constant operands needs one of them in a vector register pair.  Kept live across the render loops those
 // pairs were the registers that spilled; formed where it is used -- two moves of literals, the same issue cycles as the copy
 // of a pair that the accumulating FMA needs anyway -- it occupies nothing.  (The empty asm keeps the halves from being hoisted.)
@@ -115,6 +119,40 @@ PTMI_HD double local_constant(double k)
 #else
     return k;
 #endif
+}
+
+// The two polynomials of sinf / cosf on the reduced argument: S = sine-type of xs (= +-x, the quadrant's sign already on it), Cp = cosine-type,
+// each rounded to binary32.  One definition for sincos_t and for the quadrant-by-comparison form below: same operations, same order.
+template <bool FUSED>
+PTMI_HD void sincos_polynomials(double x2, double xs, float &S, float &Cp)
+{
+    if (FUSED) {
+        const double x3 = xs * x2;
+        const double s1 = __builtin_fma(x2, -0x1.994eb3774cf24p-13, local_constant(0x1.1107605230bc4p-7));
+        const double x7 = x3 * x2;
+        const double s = __builtin_fma(x3, -0x1.555545995a603p-3, xs);
+        S = (float)__builtin_fma(x7, s1, s);
+        const double x4 = x2 * x2;
+        const double c2 = __builtin_fma(x2, 0x1.99343027bf8c3p-16, local_constant(-0x1.6c087e89a359dp-10));
+        const double c1 = __builtin_fma(x2, -0x1.ffffffd0c621cp-2, 0x1p0);
+        const double x6 = x4 * x2;
+        const double c = __builtin_fma(x4, 0x1.55553e1068f19p-5, c1);
+        Cp = (float)__builtin_fma(x6, c2, c);
+    } else {
+        // sine-type polynomial (identical coefficients in both table rows)
+        const double x3 = xs * x2;
+        const double s1 = 0x1.1107605230bc4p-7 + x2 * -0x1.994eb3774cf24p-13;
+        const double x7 = x3 * x2;
+        const double s = xs + x3 * -0x1.555545995a603p-3;
+        S = (float)(s + x7 * s1);
+        // cosine-type polynomial; table row 1 (m & 2) negates every coefficient = negates the result
+        const double x4 = x2 * x2;
+        const double c2 = -0x1.6c087e89a359dp-10 + x2 * 0x1.99343027bf8c3p-16;
+        const double c1 = 0x1p0 + x2 * -0x1.ffffffd0c621cp-2;
+        const double x6 = x4 * x2;
+        const double c = c1 + x4 * 0x1.55553e1068f19p-5;
+        Cp = (float)(c + x6 * c2);
+    }
 }
 
 template <bool FUSED>
@@ -144,33 +182,7 @@ PTMI_HD void sincos_t(float y, float &sn, float &cs)
     const double xs = FUSED ? __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, x) ^ ((uint64_t)(((uint32_t)(m + 1) & 2u) << 30) << 32))
                             : (((m + 1) & 2) ? -x : x);
     float S, Cp;
-    if (FUSED) {
-        const double x3 = xs * x2;
-        const double s1 = __builtin_fma(x2, -0x1.994eb3774cf24p-13, local_constant(0x1.1107605230bc4p-7));
-        const double x7 = x3 * x2;
-        const double s = __builtin_fma(x3, -0x1.555545995a603p-3, xs);
-        S = (float)__builtin_fma(x7, s1, s);
-        const double x4 = x2 * x2;
-        const double c2 = __builtin_fma(x2, 0x1.99343027bf8c3p-16, local_constant(-0x1.6c087e89a359dp-10));
-        const double c1 = __builtin_fma(x2, -0x1.ffffffd0c621cp-2, 0x1p0);
-        const double x6 = x4 * x2;
-        const double c = __builtin_fma(x4, 0x1.55553e1068f19p-5, c1);
-        Cp = (float)__builtin_fma(x6, c2, c);
-    } else {
-        // sine-type polynomial (identical coefficients in both table rows)
-        const double x3 = xs * x2;
-        const double s1 = 0x1.1107605230bc4p-7 + x2 * -0x1.994eb3774cf24p-13;
-        const double x7 = x3 * x2;
-        const double s = xs + x3 * -0x1.555545995a603p-3;
-        S = (float)(s + x7 * s1);
-        // cosine-type polynomial; table row 1 (m & 2) negates every coefficient = negates the result
-        const double x4 = x2 * x2;
-        const double c2 = -0x1.6c087e89a359dp-10 + x2 * 0x1.99343027bf8c3p-16;
-        const double c1 = 0x1p0 + x2 * -0x1.ffffffd0c621cp-2;
-        const double x6 = x4 * x2;
-        const double c = c1 + x4 * 0x1.55553e1068f19p-5;
-        Cp = (float)(c + x6 * c2);
-    }
+    sincos_polynomials<FUSED>(x2, xs, S, Cp);
     // table row 1 (m & 2) negates the cosine polynomial; n & 1 swaps which polynomial is the sine.  Done on the bit
     // patterns (xor / and) instead of selects: back-to-back v_cndmask pairs are slow on gfx950.
     const uint32_t cb = f2u(Cp) ^ (((uint32_t)m & 2u) << 30), sb = f2u(S);
@@ -193,20 +205,94 @@ PTMI_HD void sincos_t(float y, float &sn, float &cs)
 #endif
 PTMI_HD void sincos(float y, float &sn, float &cs) { sincos_t<PTMI_SINCOS_FUSED != 0>(y, sn, cs); }
 
-// anglesToQuaternion (src/Util.hs:55-67) from the three HALF angles (yaw*0.5 etc. already formed)
+// ---- the quadrant by comparison: what the render kernels run for the three half angles of a bounce -------------------------------
+// reduce_fast's quadrant n = ((int32_t)(y * 2^24 * 2/pi) + 2^23) >> 24 is a monotone step function of the binary32 argument, and a bounce's
+// half angles are hk * rv with |rv| < 1 and hk = pi/2 (Matte) or (1 - p)/2 (Glossy): |y| < 1.5708 in every scene the project ships, where
+// n is -1, 0 or 1.  The first bit patterns at which n changes (tools/verify_sincos_quadrant.cpp re-derives them from the literal reduction
+// for every binary32 and refuses to pass if they are not these):
+//      0 ->  1 at kQuadT1p = 0x3f490fdb ( 0.785398185)       1 ->  2 at kQuadT2p = 0x4016cbe4 ( 2.3561945)
+//      0 -> -1 at kQuadT1n = 0xbf490fdd (-0.785398304)      -1 -> -2 at kQuadT2n = 0xc016cbe5 (-2.35619473)
+// The negative thresholds lie two ulps (T1) and one ulp (T2) further out than the positive ones: (int32_t)r truncates TOWARD ZERO and
+// the shift floors, so going down n leaves k only when r + 2^23 <= k * 2^24 - 1 (a whole unit below the multiple), going up as soon as
+// r + 2^23 >= (k + 1) * 2^24 -- in units of r's 2^-24-quadrants the negative step sits one unit further from zero.
+// Inside (kQuadT2n, kQuadT2p) two binary32 compares therefore give n, (double)n * hpi is exactly 0 or +-hpi, and the sign / negate / swap
+// of sincos_t -- (m + 1) & 2, m & 2, n & 1 with m = n -- are: flip the argument iff n = +1, negate the cosine polynomial iff n = -1, swap
+// iff n != 0.  No conversion to an integer and back, no f64 multiplication, no range skeleton.
+// The form does NOT cover |y| < 2^-12 (sn = y, cs = 1), anything at or beyond +-T2, inf or NaN: sincos3_wave_is_fast sends a wave that
+// holds one such angle in any active lane to sincos() three times.  tools/verify_sincos_quadrant.cpp (host) and
+// tools/verify_sincos_quadrant.hip (device, profiles/verify_sincos_quadrant.txt) compare it bitwise with sincos_t<false> for every binary32
+// in the range.
+constexpr uint32_t kQuadT1p = 0x3f490fdbu, kQuadT1n = 0xbf490fddu, kQuadT2p = 0x4016cbe4u, kQuadT2n = 0xc016cbe5u;
+constexpr uint32_t kQuadTiny = 0x39800000u;                                      // 2^-12: below it sincos_t returns (y, 1)
+
+// true iff the quadrant form is valid for y: kQuadT2n < y < kQuadT2p as numbers, |y| >= 2^-12; NaN and inf answer false
+PTMI_HD bool sincos_quadrant_covers(float y)
+{
+    const uint32_t b = f2u(y);
+    return (int32_t)b < (int32_t)kQuadT2p && b < kQuadT2n && (b & 0x7fffffffu) >= kQuadTiny;
+}
+
+// sin and cos of y for sincos_quadrant_covers(y); polynomials contracted as in sincos_t<true>.  For n = +-1 sincos_t's reduced argument is
+// x' = y -+ hpi and the argument of its sine polynomial, x' * sign[(n + 1) & 2], is -(y - hpi) for n = +1 and y + hpi for n = -1: both are
+// hpi - |y|, ONE binary64 subtraction with the same rounding (negation commutes with rounding; x'^2 does not see the sign).  That
+// polynomial is then the cosine, and the other one, negated iff n = -1, the sine: it takes y's sign.  For n = 0 nothing moves (x - 0 = x).
+PTMI_HD void sincos_quadrant(float y, float &sn, float &cs)
+{
+    const bool turned = y >= u2f(kQuadT1p) || y <= u2f(kQuadT1n);                // n != 0
+    const double x = (double)y;
+    const double t = 0x1.921FB54442D18p0 - __builtin_fabs(x);                    // unfused like sincos_t's (nothing here to contract)
+    const double xs = turned ? t : x;
+    const double x2 = xs * xs;
+    float S, Cp;
+    sincos_polynomials<true>(x2, xs, S, Cp);
+    const float signed_cp = u2f(f2u(Cp) ^ (f2u(y) & 0x80000000u));
+    sn = turned ? signed_cp : S;
+    cs = turned ? S : Cp;
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// One guard per wave for the three angles: every active lane's three angles inside the quadrant form's range.  On the bit patterns, so that
+// a NaN cannot hide behind a maximum: as SIGNED integers the positive floats are ordered like their values and every negative one is below
+// them (max3 < T2p: no angle at or above T2p, +inf and +NaN included); as UNSIGNED integers the negative floats are ordered by magnitude
+// above every positive one (max3 < T2n's pattern: no angle at or below T2n, -inf and -NaN included).  The smallest magnitude is a float
+// min3 of absolute values (NaN is excluded by then).
+__device__ __forceinline__ bool sincos3_wave_is_fast(float a, float b, float c)
+{
+    const int32_t ia = (int32_t)f2u(a), ib = (int32_t)f2u(b), ic = (int32_t)f2u(c);
+    const int32_t smax = ia > ib ? (ia > ic ? ia : ic) : (ib > ic ? ib : ic);
+    const uint32_t ua = f2u(a), ub = f2u(b), uc = f2u(c);
+    const uint32_t umax = ua > ub ? (ua > uc ? ua : uc) : (ub > uc ? ub : uc);
+    const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b)), __builtin_fabsf(c));
+    return __builtin_amdgcn_ballot_w64(!(smax < (int32_t)kQuadT2p && umax < kQuadT2n && amin >= u2f(kQuadTiny))) == 0;
+}
+#endif
+
+// anglesToQuaternion (src/Util.hs:55-67) from the three HALF angles (yaw*0.5 etc. already formed).  Every lane of the wave that shades is
+// here (the guard votes).
 PTMI_HD Quat quaternion_from_half_angles(float half_roll, float half_pitch, float half_yaw)
 {
     float sr, cr, sp, cp, sy, cy;
-    sincos(half_roll, sr, cr);
-#if defined(__HIP_DEVICE_COMPILE__)
-    // keep the three f64 evaluations from being interleaved: their temporaries are the kernel's VGPR peak
-    __builtin_amdgcn_sched_barrier(0);
+#if defined(__HIP_DEVICE_COMPILE__) && PTMI_SINCOS_FUSED != 0 && !defined(PTMI_SINCOS_PER_ANGLE)
+    if (__builtin_expect(sincos3_wave_is_fast(half_roll, half_pitch, half_yaw), 1)) {
+        sincos_quadrant(half_roll, sr, cr);
+        // keep the three f64 evaluations from being interleaved: their temporaries are the kernel's VGPR peak
+        __builtin_amdgcn_sched_barrier(0);
+        sincos_quadrant(half_pitch, sp, cp);
+        __builtin_amdgcn_sched_barrier(0);
+        sincos_quadrant(half_yaw, sy, cy);
+    } else
 #endif
-    sincos(half_pitch, sp, cp);
+    {
+        sincos(half_roll, sr, cr);
 #if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #endif
-    sincos(half_yaw, sy, cy);
+        sincos(half_pitch, sp, cp);
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        sincos(half_yaw, sy, cy);
+    }
     Quat q;
     q.w   = cy * cp * cr + sy * sp * sr;
     q.v.x = cy * cp * sr - sy * sp * cr;

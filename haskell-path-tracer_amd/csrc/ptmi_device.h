@@ -319,6 +319,22 @@ __device__ __forceinline__ void next_about_axis(float4 mb, V3 axis, float hk, Sf
     brdf = matte ? mb.z * nd : __builtin_fmaxf(0.0f, nd);      // mb.z = p / pi (Trace.hs:411), divided at upload
 }
 
+// -DPTMI_SINCOS_STATS (diagnostic build, tools/sincos_stats.py): called before next_about_axis with a COPY of the seed, it makes the three
+// draws again and votes as quaternion_from_half_angles will: [30] shade rounds of a wave, [31] those that leave the three-angle fast form
+// (an angle below 2^-12 in magnitude, beyond +-T2, inf or NaN in any lane that shades).  Empty and static otherwise, like diag's probes.
+#ifdef PTMI_SINCOS_STATS
+__device__ __forceinline__ void sincos3_probe(unsigned int *wc, float hk, Sfc32 seed)
+{
+#if defined(__HIP_DEVICE_COMPILE__)                                  // (the vote exists in the device pass only)
+    const float x = gen_component(seed), y = gen_component(seed), z = gen_component(seed);
+    const bool fast = sincos3_wave_is_fast(hk * x, hk * y, hk * z);
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) { atomicAdd(wc + 30, 1u); if (!fast) atomicAdd(wc + 31, 1u); }
+#endif
+}
+#else
+__device__ __forceinline__ static void sincos3_probe(unsigned int *, float, const Sfc32 &) {}
+#endif
+
 template <typename ScenePtr>
 __device__ __forceinline__ void next_direction(ScenePtr M, int idx, V3 normal, V3 d, Sfc32 &seed, V3 &next, float &brdf)
 {

@@ -11,6 +11,8 @@
 //   -DPTMI_TAIL_PHASES      ... cycles in the refill block and in the trips that end an item
 //   -DPTMI_SPLIT_STATS   streams_split_kernel: lane participation per round, wave durations      tools/split_stats.py
 //   -DPTMI_SPLIT_ENDS       ... only when its waves end (two atomics per wave)                    tools/split_stats.py ends
+//   -DPTMI_SINCOS_STATS  render_inline_kernel: shade rounds that leave the three-angle fast sin/cos   tools/sincos_stats.py
+//                        (the probe needs the draws and lives beside them: sincos3_probe, ptmi_device.h)
 // (-DPTMI_POOL_STATS belongs to an ablation kernel and lives beside it, ptmi_inline_ablations.hip.)
 #pragma once
 

@@ -116,6 +116,7 @@
                     phase.shade(pending);
                     if (pending) {
                         V3 next; float brdf;
+                        sincos3_probe(a.work_counter, hk, seed);
                         next_about_axis(mb, axis, hk, seed, next, brdf);
                         apply_bounce(M, idx, pos, next, brdf, pos, d, throughput, result);
                         ++it; ++live;

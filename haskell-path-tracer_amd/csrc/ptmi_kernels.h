@@ -331,6 +331,7 @@ hipError_t launch_stitch(const float *src, int rows, int width, int stripe_rows,
                          float *r, float *g, float *b, hipStream_t stream);
 hipError_t launch_present(Planes p, long long n, int iterations, float *rgb, uint32_t *rgba, hipStream_t stream);
 hipError_t launch_eval_sincos(const float *x, int n, float *s, float *c, hipStream_t stream);
+hipError_t launch_eval_quaternion(const float *half_angles, int n, float *q_out, hipStream_t stream);
 
 // A launch that reports ITS OWN status.  `kernel<<<...>>>(...)` drops hipLaunchKernel's result, and hipGetLastError() afterwards hands out the
 // thread's STICKY error -- the last failure of any runtime call, this library's or another's (an allocation the caller recovered from, an error

@@ -186,6 +186,17 @@ __global__ void __launch_bounds__(kBlock) eval_sincos_kernel(const float *x, int
     s[i] = sn; c[i] = cs;
 }
 
+// quaternion_from_half_angles through the inline function the render kernels use; input i belongs to lane i & 63 of its wave, so a
+// caller chooses which angles share a wave (the wave guard of the three-angle sin/cos votes over them)
+__global__ void __launch_bounds__(kBlock) eval_quaternion_kernel(const float *half_angles, int n, float *q_out)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const Quat q = quaternion_from_half_angles(half_angles[3 * (size_t)i], half_angles[3 * (size_t)i + 1], half_angles[3 * (size_t)i + 2]);
+    float *o = q_out + 4 * (size_t)i;
+    o[0] = q.w; o[1] = q.v.x; o[2] = q.v.y; o[3] = q.v.z;
+}
+
 // Quads by decreasing recorded cost, in 256 cost classes (order inside a class does not matter): one workgroup,
 // LDS histogram, scan, scatter.  n is a few thousand to a few ten thousand.  Every cost is read ONCE and its class
 // kept in `cls`, so the result is a permutation even if somebody were still adding to the costs.
@@ -311,6 +322,12 @@ hipError_t launch_eval_sincos(const float *x, int n, float *s, float *c, hipStre
 {
     if (n <= 0) return hipSuccess;
     return launch(eval_sincos_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, x, n, s, c);
+}
+
+hipError_t launch_eval_quaternion(const float *half_angles, int n, float *q_out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    return launch(eval_quaternion_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, half_angles, n, q_out);
 }
 
 

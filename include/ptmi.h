@@ -735,6 +735,10 @@ int ptmi_eval_distance_to_plane(ptmi_ctx *ctx, const ptmi_plane *planes, const f
 int ptmi_eval_check_hit(ptmi_ctx *ctx, const float *rays, int n, float *t_out, int32_t *idx_out, int32_t *just_out);
 /* sin/cos of the device math used by anglesToQuaternion, for pinning against libm. */
 int ptmi_eval_sincos(ptmi_ctx *ctx, const float *x, int n, float *sin_out, float *cos_out);
+/* anglesToQuaternion's second half (src/Util.hs:62-67) on the DEVICE, through the inline function the render kernels call: n host triples
+ * of HALF angles (roll, pitch, yaw; n x 3 floats) -> q_out (n x 4 floats: w, x, y, z).  Inputs 64 k .. 64 k + 63 share a wave: the
+ * kernels' three-angle sin/cos takes its fast form per wave, so a caller decides which angles vote together. */
+int ptmi_eval_quaternion(ptmi_ctx *ctx, const float *half_angles, int n, float *q_out);
 
 #ifdef __cplusplus
 }

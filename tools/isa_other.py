@@ -114,6 +114,8 @@ def role_of(b, inner):
         return "sphere_candidate"                  # the fold update behind the square root
     if has("v_div_scale_f32") and (inner or has("v_cmp_nle_f32")):
         return "plane_test"                        # a dense pass of the plane fold: the division and the fold's compare (in the plane loop, and once behind it)
+    if has("v_cvt_f64_f32") and has("v_fma_f64", "v_fmac_f64") and not has("v_cvt_i32_f64"):
+        return "sincos3_fast"                      # the quadrant by comparison, all three evaluations of a shade in one block (no conversion to an integer)
     if has("v_cvt_f64_f32") or has("v_cvt_i32_f64"):
         return "sincos_reduce"
     if has("v_fma_f64", "v_fmac_f64", "v_mul_f64"):
@@ -166,18 +168,25 @@ def main():
                     other_ops[key] = other_ops.get(key, 0) + 1
         table.append({"label": label, "code": code, "valu": sum(counts.values()), "counts": counts, "other_ops": other_ops, "inner": len(loops) > 1})
     roles = {}
-    order = ["sphere_test", "sphere_candidate", "plane_test", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
+    order = ["sphere_test", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
     for b in table:
         r = role_of(b, b["inner"]) or "rest_of_loop"
         roles.setdefault(r, []).append(b)
     # executions of ONE copy of a role's code per launch.  A role with k copies in the kernel (unrolled sites, the three sin/cos evaluations) runs
     # each copy (role executions / k) times; all copies hold the same instructions, so instructions per launch = mean static count x role executions
     e = execs or {}
+    # a kernel with the three-angle fast form runs sincos()'s blocks only in the shade rounds whose vote leaves it (tools/sincos_stats.py
+    # counts them; a --slow-rounds=N argument, else the share it measured on C2, 0.27: S16 holds a Glossy sphere with p = 1, whose half angles are all 0)
+    fast_form = any(role_of(b, b["inner"]) == "sincos3_fast" for b in table)
+    slow_arg = next((a for a in sys.argv[1:] if a.startswith("--slow-rounds=")), None)
+    slow_rounds = (float(slow_arg.split("=")[1]) if slow_arg else 0.27 * e.get("shade", 0.0)) if fast_form else e.get("shade", 0.0)
     role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_candidate": e.get("sphere_sqrt_path"), "plane_test": e.get("plane_passes", e.get("plane_division_path")),
-                  "sincos_reduce": 3 * e["shade"] if e else None, "sincos_polynomial": 3 * e["shade"] if e else None, "hit_normal": None,
+                  "sincos3_fast": e["shade"] - slow_rounds if e else None, "sincos_reduce": 3 * slow_rounds if e else None,
+                  "sincos_polynomial": 3 * slow_rounds if e else None, "hit_normal": None,
                   "rest_of_loop": e.get("trips"), "sqrt_slow": 0, "division_fallback": 0}
     what = {"sphere_test": "distanceTo @Sphere, the part every lane runs (16 f32 operations, the candidate test)", "sphere_candidate": "... its square root, t and the fold update, when a lane of the wave can be hit",
-            "plane_test": "distanceTo @Plane: a dense pass of the plane fold (each lane on its own stashed plane), IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade",
+            "plane_test": "distanceTo @Plane: a dense pass of the plane fold (each lane on its own stashed plane), IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade (with the fast form: per shade round that leaves it)",
+            "sincos3_fast": "sin/cos of a shade's three half angles, quadrant by comparison: cvt, hpi - |x|, selects, the two f64 polynomials (the vote's 6 instructions sit with the draws, in rest_of_loop)",
             "sincos_polynomial": "sin/cos: the two f64 polynomials, sign and swap by bit operations", "hit_normal": "hit: the sphere normal's three divisions by one length",
             "rest_of_loop": "everything else in the loop, booked at ONE execution per trip: flags and masks, frozen check and finish, restart, draws, rotation, apply_bounce",
             "sqrt_slow": "compiler's scaled square root (a lane with 0 < x < 2^-96): practically never", "division_fallback": "compiler divisions behind range checks (huge or zero operands, inf / NaN): practically never"}
@@ -201,6 +210,8 @@ def main():
             copies = max(1, sum(1 for b in bs if any(i.startswith("v_div_fixup") for i in b["code"])))
         elif r in ("sincos_reduce", "sincos_polynomial"):
             copies = 3
+        elif r == "sincos3_fast":
+            copies = len(bs)
         else:
             copies = 1
         if r == "hit_normal":
