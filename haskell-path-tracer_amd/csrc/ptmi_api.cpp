@@ -1,190 +1,20 @@
-// ptmi_api.cpp -- the C ABI of include/ptmi.h: context, device planes, scene packing, launches.
+// ptmi_api.cpp -- the C ABI of include/ptmi.h: context, device planes, options, launches, the chain and the queries (the scene's calls
+// are ptmi_scene.cpp's; ptmi_ctx.h is what the two share).
 // Compiled with hipcc together with the kernel units (ptmi_*.hip) into libptmi.so.  There is no CPU
 // fallback here: without a HIP device ptmi_create fails with PTMI_ENODEVICE.
-#include "../../include/ptmi.h"
-
-#include <hip/hip_runtime.h>
+#include "ptmi_ctx.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <atomic>
-#include <cstring>
-#include <memory>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
-
-#include "ptmi_bvh.h"
-#include "ptmi_bvh_box.h"
-#include "ptmi_bvh_spatial.h"
-#include "ptmi_mesh.h"
-#include "ptmi_mesh_box.h"
-#include "ptmi_mesh_morton.h"
-#include "ptmi_kernels.h"
-#include "ptmi_stage.h"
 
 using namespace ptmi;
 
 // render Inline with contracted arithmetic: the second object made from ptmi_inline.hip (see its last lines)
 extern "C" int ptmi_contracted_launch_inline(const void *args, int variant, void *stream);
-
-// A device block of the context: null <=> 0 bytes.  grow() and release() below keep that, and that nothing the stream may still read is freed.
-struct DeviceBlock {
-    void *p = nullptr;
-    size_t bytes = 0;
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-struct ptmi_ctx {
-    std::mutex mu;
-    int device = 0;
-    std::string err;
-
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-
-    int width = 0, height = 0;
-    int stripe_rows = 0, n_parts = 1, part = 0;   // stripe_rows == 0: one part holds everything
-    int rows_local = 0;
-
-    Planes owned{};          // seven planes carved from owned_block
-    DeviceBlock owned_block;
-    Planes bound{};
-    bool use_bound = false;
-
-    DeviceBlock d_scene;     // float4s: pack_scene
-    int n_spheres = 0, n_planes = 0;
-    // a BVH scene (ptmi_set_scene_bvh): d_scene as ever, and the hierarchy -- nodes, the spheres in leaf order, their indices -- in d_bvh
-    bool scene_bvh = false;
-    DeviceBlock d_bvh;
-    BvhView bvh{};
-    // a mesh scene (ptmi_set_scene_mesh): d_scene with the triangles' materials too, the sphere hierarchy in d_bvh (bvh), and the
-    // triangle hierarchy -- nodes, the records in leaf order, their indices, the records by index -- in d_mesh
-    bool scene_mesh = false;
-    DeviceBlock d_mesh;
-    MeshView mesh{};
-    // ... and what moving its vertices needs (ptmi_update_mesh_vertices): a second block of d_mesh's layout that an update writes and then
-    // SWAPS with d_mesh (a failed update leaves the scene as it was); the refit's plan -- kRefitWords result words, the triangles' leaf
-    // positions, the nodes level by level (MeshRefitPlan) -- in d_refit; the staged vertices of the host-pointer entry
-    DeviceBlock d_mesh_shadow, d_refit, d_refit_staging;
-    size_t mesh_nodes_f4 = 0, mesh_geom_f4 = 0, mesh_index_f4 = 0;   // d_mesh: nodes | records in leaf order | indices | records by index
-    size_t refit_leaf_pos_at = 0, refit_levels_at = 0;               // d_refit: byte offsets
-    std::vector<int32_t> refit_level_first;
-    bool fixed_has_glass = false;                                    // GLASS among the mesh scene's spheres and planes (ptmi_set_mesh_triangles keeps them)
-    // ... and what moving or replacing the spheres of a BVH or mesh scene needs (ptmi_update_spheres, ptmi_set_bvh_spheres): second blocks of
-    // d_bvh's and d_scene's layout that an update writes and then SWAPS with them (made at the first update: full copies, of which an
-    // update rewrites every box, every sphere record and the sphere rows); kSphWords result words and the sphere nodes level by level
-    // (BvhLevelPlan) in d_bvh_plan; the staged spheres of the host-pointer entries
-    DeviceBlock d_bvh_shadow, d_scene_shadow, d_bvh_plan, d_sphere_staging;
-    size_t bvh_nodes_f4 = 0;                                         // d_bvh: nodes | spheres in leaf order | indices
-    std::vector<int32_t> bvh_level_first;
-    int opt_bvh_build = PTMI_BVH_BUILD_EQUAL_COUNT;   // PTMI_OPT_BVH_DEVICE_BUILD: which tree ptmi_set_bvh_spheres builds
-    bool planes_have_glass = false, triangles_have_glass = false;    // GLASS among what ptmi_set_bvh_spheres keeps
-
-    DeviceBlock d_live;      // unsigned long long
-    DeviceBlock d_work;      // unsigned int
-    DeviceBlock d_iters;     // unsigned int
-    uint64_t nominal = 0, samples = 0;
-
-    bool timing = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_snap = nullptr;
-    // The stream form's tail (render_streams_wavefront): the end of the dispatch order is rendered by the per-pixel kernel on a
-    // stream of its own, beside the persistent launch.  d_tail_start: where that end begins (written by the order kernel).
-    hipStream_t tail_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    DeviceBlock d_tail_start;   // unsigned int
-    int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
-    bool ev_valid = false;
-    int variant = kVariantAuto;
-    Stager stager;                          // pinned ring + worker threads for host-buffer entry points (ptmi_stage.h)
-
-    // cost-ordered dispatch of the tiled kernels: what every quad of tiles cost in the last launch with this key, and
-    // the order (most expensive first) later launches with the same key use.  order_state = launches made with this key
-    DeviceBlock d_quad_cost, d_quad_order, d_quad_class;   // unsigned int per quad
-    int order_state = 0;
-    DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup
-    unsigned int chunk_capacity = 0;           // ... that many (the ticket counter's line follows)
-    struct OrderKey { ptmi_camera cam; uint64_t scene_version; int dims[8]; } order_key{};
-    uint64_t scene_version = 0;
-
-    // scratch for ptmi_render1 / point queries
-    DeviceBlock scratch;
-
-    // wavefront Streams (scenes with the GLASS extension): two ray streams + {next length, dropped}
-    bool has_glass = false;
-    DeviceBlock queue_block;
-    size_t queue_capacity = 0;       // ... rays per stream
-    DeviceBlock hit_block;           // stream form: the start hits of the pixels, in regions (HitList)
-    size_t hit_capacity = 0;         // ... slots
-    DeviceBlock d_hit_counts;        // ... records per region (unsigned int)
-    DeviceBlock d_hit_missed;        // ... and the pixels of every region that have none (unsigned long long)
-    unsigned int hit_regions = 0;
-    // The start-hit list is a function of (camera, scene, shape, partition, dispatch order) only -- every sample of a pixel
-    // shoots the same primary ray, in every call -- so it is kept until one of them changes.
-    struct HitKey { ptmi_camera cam; uint64_t scene_version, order_generation; int dims[8]; unsigned int region_slots; int cap_allows_split; const void *planes_r; } hit_key{};
-    bool hit_list_valid = false;
-    uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
-    uint64_t hit_split_pixels = 0;          // pixels whose glass primary hit the list replaced by its children's hits
-    DeviceBlock d_snapshots;         // stream form, split kernel: the seed every item starts from
-    int cus = 0;                     // compute units of the device (persistent grids)
-    size_t device_memory = (size_t)64 << 30;   // bytes of the device (budget of the stream form's seed snapshots)
-    DeviceBlock tree_stack;          // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
-    DeviceBlock d_region_done;       // stream form, ordered passes: items published per region (unsigned int)
-    int opt_ordered_passes = 0;      // PTMI_OPT_ORDERED_PASSES: 0 = automatic, 1 = off, k = k passes
-    int opt_pass_handoff = 0;        // PTMI_OPT_PASS_HANDOFF: 0 = release / acquire once per (region, pass); 1 = the fence-free write-through hand-off
-    DeviceBlock d_pass_first;        // stream form, split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
-    std::vector<int> pass_first_host;   // ... what the device block holds
-    DeviceBlock d_qcount;            // stream form: kLvWords counter words (unsigned int)
-    uint64_t rays_dropped = 0;
-    uint64_t rays_truncated = 0;
-    uint64_t rays_spilled = 0;       // stream form: children that found the wave's ring full and went through HBM
-    uint64_t rays_overflowed = 0;    // ... and its spill queue too: traced by an overflow level
-    DeviceBlock spill_block;         // stream form: the waves' spill queues
-    uint64_t live_host = 0;        // live rays counted on the host (wavefront path)
-    DeviceBlock d_stream_counters;   // kScWords device counters of the per-pixel Streams kernels
-
-    // options of render Streams (ptmi_set_option)
-    int opt_seed_rule = PTMI_SEED_AUTO;              // resolved per scene: effective_seed_rule()
-    int opt_step_cap = kStreamStepCapDefault;
-    int opt_capacity = 4;
-    int grown_capacity = 0;                          // stream form with GLASS: rays per pixel the overflow streams have been GROWN to after a call would have dropped children (0: never)
-    DeviceBlock colour_backup;                       // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
-    int opt_form = PTMI_FORM_AUTO;
-    int opt_batch = 0;
-    int opt_spp_chunks = 0;                    // 0 = automatic
-    int opt_arithmetic = PTMI_ARITH_EXACT;
-    int opt_glass_batch = 0;                   // PTMI_OPT_GLASS_BATCH: 0 = automatic, 1 = off, k = GLASS hits wait until k are pending in their wave
-    int opt_graded = 1;                        // PTMI_OPT_STREAM_GRADED: the split kernel's passes shrink towards the end of the launch
-    int opt_snapshot_mb = 0;                   // PTMI_OPT_SNAPSHOT_BUDGET_MB: 0 = an eighth of the device's memory
-    int opt_pass_groups = 0;                  // PTMI_OPT_STREAM_PASS_GROUPS: 0 = automatic, 1 = off, k = the last k passes are handed out region by region
-
-    // The chained closure (ptmi_render1_chained): the RenderResults the caller holds tokens for.  A state's seven planes are one device
-    // block (carve), or -- once it had to make room -- one host block of the same layout.  Blocks of released states wait in chain_free.
-    struct ChainState {
-        uint64_t token = 0;
-        int width = 0, height = 0;
-        void *block = nullptr;                 // device
-        std::unique_ptr<char[]> host;          // evicted: planes_bytes(n) bytes, carve's layout
-    };
-    std::vector<ChainState> chain;             // in token order (oldest first)
-    std::vector<std::pair<size_t, void *>> chain_free;   // (bytes, device block)
-    uint64_t chain_serial = 0;                 // this context's number in the process: the upper bits of its tokens
-    uint64_t chain_counter = 0;
-    int opt_chain_slots = 0;                   // PTMI_OPT_CHAIN_SLOTS: 0 = automatic
-    ptmi_chain_stats chain_stats{};
-
-    // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
-    template <class F> void each_block(F &&f)
-    {
-        for (DeviceBlock *b : {&owned_block, &d_scene, &d_bvh, &d_mesh, &d_mesh_shadow, &d_refit, &d_refit_staging, &d_bvh_shadow, &d_scene_shadow, &d_bvh_plan, &d_sphere_staging, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
-                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
-                               &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
-            f(*b);
-    }
-};
 
 namespace {
 
@@ -194,31 +24,83 @@ thread_local std::string g_create_error;
 thread_local std::string t_error;               // this thread's last failure on a context ...
 thread_local const ptmi_ctx *t_error_of = nullptr;   // ... and which
 
-int fail(ptmi_ctx *c, int code, const std::string &msg)
+}  // namespace
+
+int ptmi::fail(ptmi_ctx *c, int code, const std::string &msg)
 {
     if (c) { c->err = msg; t_error = msg; t_error_of = c; }      // (c->err: under c->mu, which every caller with a context holds)
     else g_create_error = msg;
     return code;
 }
 
-// A runtime error leaves through this library's return code -- and not, a second time, through the runtime's sticky slot (hipGetLastError
-// keeps the last failure of the thread until somebody asks: the caller's next launch check, or another library's, would find it there).
-#define PTMI_HIP(c, call)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError();                                                       \
-            return fail((c), e_ == hipErrorOutOfMemory ? PTMI_ENOMEM : PTMI_EHIP,           \
-                        std::string(#call) + ": " + hipGetErrorString(e_));                \
-        }                                                                                  \
-    } while (0)
+int ptmi::fail_hip(ptmi_ctx *c, hipError_t e, const char *call)
+{
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? PTMI_ENOMEM : PTMI_EHIP, std::string(call) + ": " + hipGetErrorString(e));
+}
+
+hipError_t ptmi::allocate(DeviceBlock &b, size_t bytes)
+{
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.bytes = bytes;
+    else { (void)hipGetLastError(); b.p = nullptr; }
+    return e;
+}
+
+void ptmi::release(DeviceBlock &b)
+{
+    if (b.p) (void)hipFree(b.p);
+    b = DeviceBlock{};
+}
+
+int ptmi::grow(ptmi_ctx *c, DeviceBlock &b, size_t bytes, const char *what)
+{
+    if (bytes <= b.bytes) return PTMI_OK;
+    if (b.p) {
+        PTMI_HIP(c, hipStreamSynchronize(c->stream));
+        release(b);
+    }
+    const hipError_t e = allocate(b, bytes);
+    if (e != hipSuccess)
+        return fail(c, e == hipErrorOutOfMemory ? PTMI_ENOMEM : PTMI_EHIP,
+                    std::string(what) + ": hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    return PTMI_OK;
+}
+
+hipError_t ptmi::copy_to_device(ptmi_ctx *c, const CopySpan *spans, int n)
+{
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += spans[i].bytes;
+    if (c->stager.threads() > 0 && total >= Stager::kMinBytes) return c->stager.to_device(spans, n, c->stream);
+    for (int i = 0; i < n; ++i) {
+        if (!spans[i].bytes) continue;
+        const hipError_t e = hipMemcpyAsync(spans[i].dev, spans[i].host, spans[i].bytes, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t ptmi::copy_to_host(ptmi_ctx *c, const CopySpan *spans, int n)
+{
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += spans[i].bytes;
+    if (c->stager.threads() > 0 && total >= Stager::kMinBytes) return c->stager.to_host(spans, n, c->stream);
+    for (int i = 0; i < n; ++i) {
+        if (!spans[i].bytes) continue;
+        const hipError_t e = hipMemcpyAsync(spans[i].host, spans[i].dev, spans[i].bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipStreamSynchronize(c->stream);
+}
+
+namespace {
 
 // PTMI_SEED_AUTO: `combine new old` (the seed of the result) wherever the reference defines the outcome -- no ray-splitting
 // material -- and the accumulator's seed with GLASS, where several results of one step would race for it
 int effective_seed_rule(const ptmi_ctx *c)
 {
     if (c->opt_seed_rule != PTMI_SEED_AUTO) return c->opt_seed_rule;
-    return c->has_glass ? PTMI_SEED_KEEP_ACCUMULATOR : PTMI_SEED_FROM_RESULT;
+    return c->scene.has_glass ? PTMI_SEED_KEEP_ACCUMULATOR : PTMI_SEED_FROM_RESULT;
 }
 
 // PTMI_OPT_STREAMS_FORM resolved: does `render Streams` run in its stream ("wavefront") form?  AUTO: only where it pays and costs nothing that
@@ -228,10 +110,10 @@ int effective_seed_rule(const ptmi_ctx *c)
 bool uses_stream_form(const ptmi_ctx *c, int algorithm, int n_parts, int n_spp)
 {
     if (algorithm != PTMI_STREAMS) return false;
-    if (c->scene_bvh || c->scene_mesh) return false;     // (a BVH or mesh scene renders through the per-pixel kernels only)
+    if (c->scene.hierarchical()) return false;     // (a BVH or mesh scene renders through the per-pixel kernels only)
     if (c->opt_form == PTMI_FORM_STREAM || c->variant == kVariantStreamForm) return true;
     if (c->opt_form == PTMI_FORM_PIXEL) return false;
-    return c->has_glass && n_parts > 1 && (n_spp < 0 || n_spp >= 256);
+    return c->scene.has_glass && n_parts > 1 && (n_spp < 0 || n_spp >= 256);
 }
 
 int effective_stripe(const ptmi_ctx *c) { return c->stripe_rows > 0 ? c->stripe_rows : (c->height > 0 ? c->height : 1); }
@@ -267,110 +149,6 @@ bool too_many_pixels(int width, int height) { return (unsigned long long)width *
 
 Planes &active(ptmi_ctx *c) { return c->use_bound ? c->bound : c->owned; }
 
-// The one allocation of a DeviceBlock (which must be empty).  On failure it stays empty and the runtime's sticky slot is cleared.
-hipError_t allocate(DeviceBlock &b, size_t bytes)
-{
-    const hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.bytes = bytes;
-    else { (void)hipGetLastError(); b.p = nullptr; }
-    return e;
-}
-
-void release(DeviceBlock &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b = DeviceBlock{};
-}
-
-// (with the mesh scene they belong to; the stream is drained)
-void release_mesh_refit(ptmi_ctx *c)
-{
-    release(c->d_mesh_shadow);
-    release(c->d_refit);
-    release(c->d_refit_staging);
-    c->refit_level_first.clear();
-}
-
-// (with the BVH or mesh scene they belong to; the stream is drained)
-void release_sphere_update(ptmi_ctx *c)
-{
-    release(c->d_bvh_shadow);
-    release(c->d_scene_shadow);
-    release(c->d_bvh_plan);
-    release(c->d_sphere_staging);
-    c->bvh_level_first.clear();
-    c->bvh_nodes_f4 = 0;
-}
-
-// c->bvh's pointers into d_bvh, whichever of the two blocks that is (and the mesh scene's copy of them)
-void point_bvh_view(ptmi_ctx *c)
-{
-    const float4 *base = c->d_bvh.as<float4>();
-    c->bvh.nodes = base;
-    c->bvh.geom = base + c->bvh_nodes_f4;
-    c->bvh.index = reinterpret_cast<const int *>(base + c->bvh_nodes_f4 + (size_t)c->n_spheres);
-    if (c->scene_mesh) c->mesh.spheres = c->bvh;
-}
-
-constexpr size_t kBvhPlanLevelsAt = 256;                   // d_bvh_plan: the result words, then the nodes by level
-
-// c->mesh's pointers into d_mesh, whichever of the two blocks that is
-void point_mesh_view(ptmi_ctx *c)
-{
-    const float4 *tb = c->d_mesh.as<float4>();
-    c->mesh.nodes = tb;
-    c->mesh.geom = tb + c->mesh_nodes_f4;
-    c->mesh.index = reinterpret_cast<const int *>(tb + c->mesh_nodes_f4 + c->mesh_geom_f4);
-    c->mesh.by_index = tb + c->mesh_nodes_f4 + c->mesh_geom_f4 + c->mesh_index_f4;
-}
-
-// `b` holds at least `bytes` (its contents are not kept).  A block that is replaced goes only once the stream is drained; with none
-// held nothing on the stream can read it (the tail stream has joined c->stream before any call returns).  If the allocation fails the
-// block is empty.
-int grow(ptmi_ctx *c, DeviceBlock &b, size_t bytes, const char *what)
-{
-    if (bytes <= b.bytes) return PTMI_OK;
-    if (b.p) {
-        PTMI_HIP(c, hipStreamSynchronize(c->stream));
-        release(b);
-    }
-    const hipError_t e = allocate(b, bytes);
-    if (e != hipSuccess)
-        return fail(c, e == hipErrorOutOfMemory ? PTMI_ENOMEM : PTMI_EHIP,
-                    std::string(what) + ": hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    return PTMI_OK;
-}
-
-// Host-buffer transfers of the boundary (stream-ordered on c->stream).  Transfers of a megabyte or more go through
-// the context's Stager (ptmi_stage.h: parallel page copies into a pinned ring, one DMA per 8-MB chunk -- the driver
-// never pins the caller's pages); small ones, or all of them when the engine is off (PTMI_STAGE_THREADS=0), are
-// plain async copies.  copy_to_host leaves the stream drained in both cases.
-hipError_t copy_to_device(ptmi_ctx *c, const CopySpan *spans, int n)
-{
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) total += spans[i].bytes;
-    if (c->stager.threads() > 0 && total >= Stager::kMinBytes) return c->stager.to_device(spans, n, c->stream);
-    for (int i = 0; i < n; ++i) {
-        if (!spans[i].bytes) continue;
-        const hipError_t e = hipMemcpyAsync(spans[i].dev, spans[i].host, spans[i].bytes, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t copy_to_host(ptmi_ctx *c, const CopySpan *spans, int n)
-{
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) total += spans[i].bytes;
-    if (c->stager.threads() > 0 && total >= Stager::kMinBytes) return c->stager.to_host(spans, n, c->stream);
-    for (int i = 0; i < n; ++i) {
-        if (!spans[i].bytes) continue;
-        const hipError_t e = hipMemcpyAsync(spans[i].host, spans[i].dev, spans[i].bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) return e;
-    }
-    return hipStreamSynchronize(c->stream);
-}
-
 // primaryRays' per-launch values (src/Scene/Trace.hs:205-242), evaluated on the host with
 // the same arithmetic definitions as the device code (ptmi_core.h); tan is the host libm's.
 PrimaryUniforms make_uniforms(const ptmi_camera &cam, int width, int height)
@@ -391,24 +169,6 @@ PrimaryUniforms make_uniforms(const ptmi_camera &cam, int width, int height)
     u.pos = c_pos; u.center = center; u.right = right; u.top = top;
     u.size_x = (float)width; u.size_y = (float)(-height);                            // Util.hs:198-200
     return u;
-}
-
-void pack_scene(const ptmi_sphere *sph, int ns, const ptmi_plane *pl, int np, std::vector<float4> &out)
-{
-    out.assign((size_t)ns + 2 * (size_t)np + 2 * ((size_t)ns + np), float4{0, 0, 0, 0});
-    size_t k = 0;
-    for (int i = 0; i < ns; ++i)
-        out[k++] = float4{sph[i].position[0], sph[i].position[1], sph[i].position[2], sph[i].radius * sph[i].radius};
-    for (int j = 0; j < np; ++j) {
-        out[k++] = float4{pl[j].position[0], pl[j].position[1], pl[j].position[2], 0.0f};
-        out[k++] = float4{pl[j].direction[0], pl[j].direction[1], pl[j].direction[2], 0.0f};
-    }
-    auto mat = [&](const float *color, float illum, int32_t tag, float p) {
-        out[k++] = float4{color[0], color[1], color[2], illum};
-        out[k++] = float4{u2f((uint32_t)tag), p, p / kPi, 0.5f * (1.0f - p)};
-    };
-    for (int i = 0; i < ns; ++i) mat(sph[i].color, sph[i].illuminance, sph[i].brdf_tag, sph[i].brdf_param);
-    for (int j = 0; j < np; ++j) mat(pl[j].color, pl[j].illuminance, pl[j].brdf_tag, pl[j].brdf_param);
 }
 
 constexpr size_t kLiveBytes = (size_t)kStatShards * kStatStride * sizeof(unsigned long long);     // sharded statistics (ptmi_kernels.h)
@@ -603,7 +363,7 @@ int StreamCall::start_hit_list(const ptmi_camera &camera)
     // the statistics accumulate on the device over the whole call; cursors start from zero
     PTMI_HIP(c, hipMemsetAsync(qcount(), 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
     ptmi_ctx::HitKey key{};
-    key.cam = camera; key.scene_version = c->scene_version; key.order_generation = a.quad_order ? c->order_generation : 0;
+    key.cam = camera; key.scene_version = c->scene.version; key.order_generation = a.quad_order ? c->order_generation : 0;
     const int key_dims[8] = {a.width, a.height, a.rows_local, a.stripe_rows, a.n_parts, a.part, a.quad_order ? 1 : 0, 0};
     std::memcpy(key.dims, key_dims, sizeof key_dims);
     key.region_slots = region_slots; key.cap_allows_split = a.stream_step_cap >= 3 ? 1 : 0; key.planes_r = nullptr;
@@ -741,13 +501,13 @@ int StreamCall::split_setup()
     it.group_first = groups < passes ? pass_first + (kMaxStreamPasses + 1) : nullptr;     // (every pass on its own needs no table)
     it.groups = groups;
     // GLASS hits wait in their lanes until that many are pending in the wave (measured: DESIGN.md 5.5); nothing to wait for without GLASS
-    it.glass_batch = !c->has_glass ? 0 : (c->opt_glass_batch > 0 ? c->opt_glass_batch : kGlassBatchDefault);
+    it.glass_batch = !c->scene.has_glass ? 0 : (c->opt_glass_batch > 0 ? c->opt_glass_batch : kGlassBatchDefault);
     it.seed_snapshots = c->d_snapshots.as<const uint4>();
     it.spill = carve_queue(c->spill_block.p, c->spill_block.bytes / ((size_t)kRayQueueWords * 4), 0);
     it.out_count = qcount() + cursor_of(0);
     it.out_base = grid * first_block;
     it.emitted = it.out_count + 2 * kCounterStride;
-    it.may_emit = c->has_glass ? 1 : 0;
+    it.may_emit = c->scene.has_glass ? 1 : 0;
 
     // `expand` (Trace.hs:284-293) makes its vectors as long as the step needs; the overflow streams here have a capacity.  A call that WOULD drop
     // children is therefore redone with longer streams: the three colour planes -- all a launch changes that the next attempt reads; the seeds moved
@@ -758,12 +518,12 @@ int StreamCall::split_setup()
     // (only while a redo is possible: with the streams at kMaxStreamRaysPerPixel already the drops would stand, and nothing is copied aside.
     // The recorded quad costs of the launch are part of what a redo must take back: the failed attempt's items added theirs.)
     cost_bytes = a.quad_cost ? (size_t)quad_positions(a.width, a.rows_local) * sizeof(unsigned int) : 0;
-    can_redo = c->has_glass && cap_rays < kMaxStreamRaysPerPixel;
+    can_redo = c->scene.has_glass && cap_rays < kMaxStreamRaysPerPixel;
     if (can_redo) {
         if (int rc = grow(c, c->colour_backup, 3 * plane_bytes + cost_bytes, "the colour backup")) return rc;
         return copy_colour(false);
     }
-    if (c->colour_backup.p && !c->has_glass) {             // the scene lost its GLASS: the three planes' worth of memory goes back
+    if (c->colour_backup.p && !c->scene.has_glass) {             // the scene lost its GLASS: the three planes' worth of memory goes back
         PTMI_HIP(c, hipStreamSynchronize(c->stream));
         release(c->colour_backup);
     }
@@ -796,7 +556,7 @@ int StreamCall::read_counters(int levels)                // the statistics and t
 int StreamCall::overflow_levels(unsigned long long &overflowed)
 {
     overflowed = 0;
-    for (int level = 0; c->has_glass && emitted_of(level) > 0u;) {
+    for (int level = 0; c->scene.has_glass && emitted_of(level) > 0u;) {
         overflowed += emitted_of(level);
         const size_t cursor = (size_t)raw[cursor_of(level)] + base[(size_t)(level % kLvMaxLevels)];
         const size_t items = cursor < capacity ? cursor : capacity;
@@ -898,7 +658,7 @@ int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_c
     const size_t n = (size_t)a.rows_local * a.width;
     if (n == 0 || n_spp <= 0) return PTMI_OK;
     if (n > 0x3ffffff0ull) return fail(c, PTMI_ELIMIT, "image too large for the stream form of Streams");   // 32-bit byte offsets into the planes
-    const bool ordered = !c->has_glass && (c->opt_batch == 0 || a.seed_from_result);
+    const bool ordered = !c->scene.has_glass && (c->opt_batch == 0 || a.seed_from_result);
     const unsigned int n_regions = streams_regions(a.width, a.rows_local);
     const unsigned int region_slots = ordered ? 64u : 128u;    // a glass primary hit contributes up to two start hits
     const size_t hit_slots = (size_t)n_regions * region_slots;
@@ -927,7 +687,7 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
 {
     RenderArgs a{};
     a.cam = make_uniforms(*camera, width, height);
-    a.scene.packed = c->d_scene.as<float4>(); a.scene.n_spheres = c->n_spheres; a.scene.n_planes = c->n_planes;
+    a.scene.packed = c->scene.packed.as<float4>(); a.scene.n_spheres = (int)c->scene.rows.ns; a.scene.n_planes = (int)c->scene.rows.np;
     a.planes = planes;
     a.screen_x = sx; a.screen_y = sy;
     a.width = width; a.height = height; a.rows_local = rows_local;
@@ -959,7 +719,7 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
                 if (int rc = grow(c, *q, quad_bytes, "the dispatch order")) return rc;
         }
         ptmi_ctx::OrderKey key{};
-        key.cam = *camera; key.scene_version = c->scene_version;
+        key.cam = *camera; key.scene_version = c->scene.version;
         const int dims[8] = {width, height, rows_local, stripe_rows, n_parts, part, bounce_limit, stream_form ? 2 : algorithm};
         std::memcpy(key.dims, dims, sizeof dims);
         if (std::memcmp(&key, &c->order_key, sizeof key) != 0) { c->order_key = key; c->order_state = 0; ++c->order_generation; }
@@ -999,24 +759,24 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
         a.spp_chunks = sx ? 1 : c->opt_spp_chunks;
     }
     if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev0, c->stream)); }
-    const BvhView *bvh = c->scene_bvh ? &c->bvh : nullptr;    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
+    const BvhView *bvh = c->scene.kind == SceneKind::Bvh ? &c->scene.bvh : nullptr;    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
     if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
         PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == kVariantStreamForm ? kVariantAuto : c->variant, c->stream));
-    } else if (algorithm == PTMI_INLINE && c->scene_mesh) {
-        PTMI_HIP(c, launch_render_inline_mesh(a, c->mesh, c->stream));
+    } else if (algorithm == PTMI_INLINE && c->scene.kind == SceneKind::Mesh) {
+        PTMI_HIP(c, launch_render_inline_mesh(a, c->scene.mesh, c->stream));
     } else if (algorithm == PTMI_INLINE) {
         PTMI_HIP(c, launch_render_inline(a, bvh, c->variant, c->stream));
     } else if (stream_form) {                              // rays travel through streams in HBM (PTMI_OPT_STREAMS_FORM; kVariantStreamForm)
         if (int rc = render_streams_wavefront(c, a, n_spp, *camera)) return rc;
-    } else if (c->has_glass) {                             // rays may split: the per-pixel tree walk
+    } else if (c->scene.has_glass) {                             // rays may split: the per-pixel tree walk
         // the first waiting children of every lane as 64-byte records in global memory (ptmi_streams_tree.hip): 16 KB per tile
         const size_t want = (size_t)tree_workgroups(width, rows_local) * kTreeFastLevels * 64 * 64;
         if (int rc = grow(c, c->tree_stack, want, "the tree walk's records of waiting children")) return rc;
         a.tree_stack = c->tree_stack.as<float4>();
-        if (c->scene_mesh) PTMI_HIP(c, launch_render_streams_tree_mesh(a, c->mesh, c->stream));
+        if (c->scene.kind == SceneKind::Mesh) PTMI_HIP(c, launch_render_streams_tree_mesh(a, c->scene.mesh, c->stream));
         else PTMI_HIP(c, launch_render_streams_tree(a, bvh, c->variant, c->stream));
-    } else if (c->scene_mesh) {
-        PTMI_HIP(c, launch_render_streams_mesh(a, c->mesh, c->stream));
+    } else if (c->scene.kind == SceneKind::Mesh) {
+        PTMI_HIP(c, launch_render_streams_mesh(a, c->scene.mesh, c->stream));
     } else {
         PTMI_HIP(c, launch_render_streams(a, bvh, c->variant, c->stream));
     }
@@ -1035,15 +795,15 @@ int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int
     if (algorithm != PTMI_INLINE && algorithm != PTMI_STREAMS) return fail(c, PTMI_EINVAL, "unknown algorithm");
     if (bounce_limit < 0) return fail(c, PTMI_EINVAL, "bounce_limit < 0");
     if (n_spp < 0) return fail(c, PTMI_EINVAL, "n_spp < 0");
-    if (!c->d_scene.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     // "features that require diverging rays like light refraction" need the stream algorithm (Trace.hs:56-67)
-    if (algorithm == PTMI_INLINE && c->has_glass)
+    if (algorithm == PTMI_INLINE && c->scene.has_glass)
         return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
-    if (algorithm == PTMI_STREAMS && c->has_glass && c->opt_seed_rule == PTMI_SEED_FROM_RESULT)
+    if (algorithm == PTMI_STREAMS && c->scene.has_glass && c->opt_seed_rule == PTMI_SEED_FROM_RESULT)
         return fail(c, PTMI_EINVAL, "PTMI_SEED_FROM_RESULT is undefined when rays split (GLASS): several results race for one pixel's seed");
-    if (c->scene_bvh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+    if (c->scene.kind == SceneKind::Bvh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
         return fail(c, PTMI_EINVAL, "a BVH scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
-    if (c->scene_mesh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+    if (c->scene.kind == SceneKind::Mesh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
         return fail(c, PTMI_EINVAL, "a mesh scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
     return PTMI_OK;
 }
@@ -1304,719 +1064,6 @@ void ptmi_destroy(ptmi_ctx *c)
     delete c;
 }
 
-int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (n_spheres < 0 || n_planes < 0 || (n_spheres > 0 && !spheres) || (n_planes > 0 && !planes))
-        return fail(c, PTMI_EINVAL, "bad scene arguments");
-    // expMinWith _ [] = error "Invalid call to 'expMinWith'"   (src/Util.hs:172)
-    if (n_spheres + n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
-    if (n_spheres + n_planes > PTMI_MAX_PRIMITIVES) return fail(c, PTMI_ELIMIT, "too many primitives");
-    for (int i = 0; i < n_spheres; ++i)
-        if (spheres[i].brdf_tag < PTMI_MATTE || spheres[i].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "sphere with unknown brdf_tag");
-    for (int j = 0; j < n_planes; ++j)
-        if (planes[j].brdf_tag < PTMI_MATTE || planes[j].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "plane with unknown brdf_tag");
-    PTMI_HIP(c, hipSetDevice(c->device));
-    std::vector<float4> packed;
-    pack_scene(spheres, n_spheres, planes, n_planes, packed);
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    // the new scene stands complete before the old one goes: a failure here leaves the context with the scene (and the counts) it had
-    DeviceBlock fresh;
-    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
-    hipError_t e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed` dies at return
-    if (e != hipSuccess) { release(fresh); PTMI_HIP(c, e); }
-    release(c->d_scene);
-    release(c->d_bvh);
-    release(c->d_mesh);
-    release_mesh_refit(c);
-    release_sphere_update(c);
-    c->d_scene = fresh;
-    c->scene_bvh = false; c->bvh = BvhView{};
-    c->scene_mesh = false; c->mesh = MeshView{};
-    c->n_spheres = n_spheres; c->n_planes = n_planes;
-    ++c->scene_version;
-    c->has_glass = false;
-    for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
-    for (int j = 0; j < n_planes; ++j) c->has_glass |= planes[j].brdf_tag == PTMI_GLASS;
-    return PTMI_OK;
-}
-
-int ptmi_set_scene_bvh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-#ifdef PTMI_ABLATIONS
-    (void)spheres; (void)n_spheres; (void)planes; (void)n_planes;
-    return fail(c, PTMI_EINVAL, "the ablation library has no BVH kernels: use libptmi for BVH scenes");
-#else
-    if (n_spheres < 0 || n_planes < 0 || (n_spheres > 0 && !spheres) || (n_planes > 0 && !planes))
-        return fail(c, PTMI_EINVAL, "bad scene arguments");
-    if (n_spheres + n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
-    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
-    if (n_planes > PTMI_MAX_BVH_PLANES) return fail(c, PTMI_ELIMIT, "more planes than PTMI_MAX_BVH_PLANES");
-    if (c->variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
-    if (c->opt_form == PTMI_FORM_STREAM)
-        return fail(c, PTMI_EINVAL, "a BVH scene has no stream form: set PTMI_OPT_STREAMS_FORM to PTMI_FORM_AUTO or PTMI_FORM_PIXEL first");
-    for (int i = 0; i < n_spheres; ++i)
-        if (spheres[i].brdf_tag < PTMI_MATTE || spheres[i].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "sphere with unknown brdf_tag");
-    for (int j = 0; j < n_planes; ++j)
-        if (planes[j].brdf_tag < PTMI_MATTE || planes[j].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "plane with unknown brdf_tag");
-    BvhBuild bb;
-    std::string why;
-    if (int rc = bvh_build(spheres, n_spheres, bb, &why)) return fail(c, rc, why);
-    PTMI_HIP(c, hipSetDevice(c->device));
-    std::vector<float4> packed;
-    pack_scene(spheres, n_spheres, planes, n_planes, packed);
-    // d_bvh: the nodes (four float4 each), the spheres in leaf order as pack_scene makes them, their original indices
-    const size_t nodes_f4 = bb.nodes.size() * 4, geom_f4 = (size_t)n_spheres;
-    std::vector<float4> hier(nodes_f4 + geom_f4 + ((size_t)n_spheres + 3) / 4);
-    std::memcpy(hier.data(), bb.nodes.data(), bb.nodes.size() * sizeof(ptmi_bvh_node));
-    for (int k = 0; k < n_spheres; ++k) hier[nodes_f4 + (size_t)k] = packed[(size_t)bb.order[(size_t)k]];
-    if (n_spheres > 0) std::memcpy(&hier[nodes_f4 + geom_f4], bb.order.data(), (size_t)n_spheres * sizeof(int32_t));
-    // d_bvh_plan: what ptmi_update_spheres needs of this hierarchy (the result words, the nodes by level)
-    BvhLevelPlan plan;
-    bvh_level_plan(bb.nodes, plan);
-    std::vector<char> plan_block(kBvhPlanLevelsAt + plan.level_nodes.size() * sizeof(int32_t), 0);
-    std::memcpy(&plan_block[kBvhPlanLevelsAt], plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    // all blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
-    DeviceBlock fresh, fresh_bvh, fresh_plan;
-    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
-    hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_plan, plan_block.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_plan.p, plan_block.data(), fresh_plan.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier` and `plan_block` die at return
-    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_plan); PTMI_HIP(c, e); }
-    release(c->d_scene);
-    release(c->d_bvh);
-    release(c->d_mesh);
-    release_mesh_refit(c);
-    release_sphere_update(c);
-    c->d_scene = fresh;
-    c->d_bvh = fresh_bvh;
-    c->d_bvh_plan = fresh_plan;
-    c->bvh_nodes_f4 = nodes_f4;
-    c->bvh_level_first = std::move(plan.level_first);
-    c->scene_bvh = true;
-    c->scene_mesh = false; c->mesh = MeshView{};
-    c->n_spheres = n_spheres; c->n_planes = n_planes;
-    point_bvh_view(c);
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
-    ++c->scene_version;
-    c->has_glass = false;
-    c->planes_have_glass = c->triangles_have_glass = false;
-    for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
-    for (int j = 0; j < n_planes; ++j) c->planes_have_glass |= planes[j].brdf_tag == PTMI_GLASS;
-    c->has_glass |= c->planes_have_glass;
-    return PTMI_OK;
-#endif
-}
-
-int ptmi_set_scene_mesh(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const ptmi_triangle *triangles, int n_triangles,
-                        const ptmi_plane *planes, int n_planes)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-#ifdef PTMI_ABLATIONS
-    (void)spheres; (void)n_spheres; (void)triangles; (void)n_triangles; (void)planes; (void)n_planes;
-    return fail(c, PTMI_EINVAL, "the ablation library has no mesh kernels: use libptmi for mesh scenes");
-#else
-    if (n_spheres < 0 || n_planes < 0 || n_triangles < 0 || (n_spheres > 0 && !spheres) || (n_planes > 0 && !planes) ||
-        (n_triangles > 0 && !triangles))
-        return fail(c, PTMI_EINVAL, "bad scene arguments");
-    if ((long long)n_spheres + n_planes + n_triangles == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
-    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
-    if (n_planes > PTMI_MAX_BVH_PLANES) return fail(c, PTMI_ELIMIT, "more planes than PTMI_MAX_BVH_PLANES");
-    if (n_triangles > PTMI_MAX_MESH_TRIANGLES) return fail(c, PTMI_ELIMIT, "more triangles than PTMI_MAX_MESH_TRIANGLES");
-    if (c->variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels: ptmi_set_variant(ctx, 0) first");
-    if (c->opt_form == PTMI_FORM_STREAM)
-        return fail(c, PTMI_EINVAL, "a mesh scene has no stream form: set PTMI_OPT_STREAMS_FORM to PTMI_FORM_AUTO or PTMI_FORM_PIXEL first");
-    if (c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
-        return fail(c, PTMI_EINVAL, "a mesh scene has no contracted-arithmetic kernel: set PTMI_OPT_ARITHMETIC back first");
-    for (int i = 0; i < n_spheres; ++i)
-        if (spheres[i].brdf_tag < PTMI_MATTE || spheres[i].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "sphere with unknown brdf_tag");
-    for (int j = 0; j < n_planes; ++j)
-        if (planes[j].brdf_tag < PTMI_MATTE || planes[j].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "plane with unknown brdf_tag");
-    for (int k = 0; k < n_triangles; ++k)
-        if (triangles[k].brdf_tag < PTMI_MATTE || triangles[k].brdf_tag > PTMI_GLASS)
-            return fail(c, PTMI_EINVAL, "triangle with unknown brdf_tag");
-    BvhBuild bb;
-    MeshBuild mb;
-    std::string why;
-    if (int rc = bvh_build(spheres, n_spheres, bb, &why)) return fail(c, rc, why);
-    if (int rc = mesh_build(triangles, n_triangles, mb, &why)) return fail(c, rc, why);
-    PTMI_HIP(c, hipSetDevice(c->device));
-    // d_scene: pack_scene's spheres and planes, then the materials of spheres, planes and triangles (primitive ns + np + k)
-    std::vector<float4> packed;
-    pack_scene(spheres, n_spheres, planes, n_planes, packed);
-    packed.reserve(packed.size() + 2 * (size_t)n_triangles);
-    for (int k = 0; k < n_triangles; ++k) {
-        const ptmi_triangle &t = triangles[k];
-        const float p = t.brdf_param;
-        packed.push_back(float4{t.color[0], t.color[1], t.color[2], t.illuminance});
-        packed.push_back(float4{u2f((uint32_t)t.brdf_tag), p, p / kPi, 0.5f * (1.0f - p)});
-    }
-    // d_bvh: as ptmi_set_scene_bvh makes it
-    const size_t nodes_f4 = bb.nodes.size() * 4, geom_f4 = (size_t)n_spheres;
-    std::vector<float4> hier(nodes_f4 + geom_f4 + ((size_t)n_spheres + 3) / 4);
-    std::memcpy(hier.data(), bb.nodes.data(), bb.nodes.size() * sizeof(ptmi_bvh_node));
-    for (int k = 0; k < n_spheres; ++k) hier[nodes_f4 + (size_t)k] = packed[(size_t)bb.order[(size_t)k]];
-    if (n_spheres > 0) std::memcpy(&hier[nodes_f4 + geom_f4], bb.order.data(), (size_t)n_spheres * sizeof(int32_t));
-    // d_mesh: the triangle nodes (four float4 each), the kept triangles in leaf order (three float4 each), their original indices, and
-    // every triangle by original index (three float4 each)
-    const size_t kept = mb.order.size();
-    const size_t tn_f4 = mb.nodes.size() * 4, tg_f4 = 3 * kept, ti_f4 = (kept + 3) / 4, tb_f4 = 3 * (size_t)n_triangles;
-    std::vector<float4> tri(tn_f4 + tg_f4 + ti_f4 + tb_f4);
-    std::memcpy(tri.data(), mb.nodes.data(), mb.nodes.size() * sizeof(ptmi_bvh_node));
-    for (size_t k = 0; k < kept; ++k)
-        std::memcpy(&tri[tn_f4 + 3 * k], &mb.records[(size_t)mb.order[k] * 12], 12 * sizeof(float));
-    if (kept > 0) std::memcpy(&tri[tn_f4 + tg_f4], mb.order.data(), kept * sizeof(int32_t));
-    if (n_triangles > 0) std::memcpy(&tri[tn_f4 + tg_f4 + ti_f4], mb.records.data(), (size_t)n_triangles * 12 * sizeof(float));
-    // d_refit: what ptmi_update_mesh_vertices needs of this hierarchy (the result words, the leaf positions, the nodes by level)
-    MeshRefitPlan plan;
-    mesh_refit_plan(mb, n_triangles, plan);
-    const size_t leaf_pos_at = 256, levels_at = leaf_pos_at + (((size_t)n_triangles * sizeof(int32_t) + 255) / 256) * 256;
-    std::vector<char> refit(levels_at + plan.level_nodes.size() * sizeof(int32_t), 0);
-    if (n_triangles > 0) std::memcpy(&refit[leaf_pos_at], plan.leaf_pos.data(), (size_t)n_triangles * sizeof(int32_t));
-    std::memcpy(&refit[levels_at], plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t));
-    // d_bvh_plan: as ptmi_set_scene_bvh makes it
-    BvhLevelPlan sphere_plan;
-    bvh_level_plan(bb.nodes, sphere_plan);
-    std::vector<char> plan_block(kBvhPlanLevelsAt + sphere_plan.level_nodes.size() * sizeof(int32_t), 0);
-    std::memcpy(&plan_block[kBvhPlanLevelsAt], sphere_plan.level_nodes.data(), sphere_plan.level_nodes.size() * sizeof(int32_t));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    // all blocks stand complete before the old scene goes: a failure here leaves the context with the scene it had
-    DeviceBlock fresh, fresh_bvh, fresh_mesh, fresh_shadow, fresh_refit, fresh_plan;
-    PTMI_HIP(c, allocate(fresh, packed.size() * sizeof(float4)));
-    hipError_t e = allocate(fresh_bvh, hier.size() * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_plan, plan_block.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_plan.p, plan_block.data(), fresh_plan.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = allocate(fresh_mesh, tri.size() * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_shadow, tri.size() * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_refit, refit.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, packed.data(), fresh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_bvh.p, hier.data(), fresh_bvh.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_mesh.p, tri.data(), fresh_mesh.bytes, hipMemcpyHostToDevice, c->stream);
-    // (the second block starts as a copy: an update rewrites every record and every box of it, the references and indices never move)
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_shadow.p, fresh_mesh.p, fresh_mesh.bytes, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_refit.p, refit.data(), fresh_refit.bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `packed`, `hier`, `tri` and `refit` die at return
-    if (e != hipSuccess) { release(fresh); release(fresh_bvh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); release(fresh_plan); PTMI_HIP(c, e); }
-    release(c->d_scene);
-    release(c->d_bvh);
-    release(c->d_mesh);
-    release_mesh_refit(c);
-    release_sphere_update(c);
-    c->d_scene = fresh;
-    c->d_bvh = fresh_bvh;
-    c->d_bvh_plan = fresh_plan;
-    c->bvh_nodes_f4 = nodes_f4;
-    c->bvh_level_first = std::move(sphere_plan.level_first);
-    c->d_mesh = fresh_mesh;
-    c->d_mesh_shadow = fresh_shadow;
-    c->d_refit = fresh_refit;
-    c->mesh_nodes_f4 = tn_f4; c->mesh_geom_f4 = tg_f4; c->mesh_index_f4 = ti_f4;
-    c->refit_leaf_pos_at = leaf_pos_at; c->refit_levels_at = levels_at;
-    c->refit_level_first = std::move(plan.level_first);
-    c->scene_bvh = false;
-    c->scene_mesh = true;
-    c->bvh = BvhView{};
-    c->mesh = MeshView{};
-    c->n_spheres = n_spheres; c->n_planes = n_planes;
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = bb.lo[a]; c->bvh.hi[a] = bb.hi[a]; }
-    point_bvh_view(c);                                     // (and mesh.spheres)
-    point_mesh_view(c);
-    c->mesh.n_triangles = n_triangles;
-    c->mesh.n_kept = (int)kept;
-    for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = mb.lo[a]; c->mesh.hi[a] = mb.hi[a]; }
-    ++c->scene_version;
-    c->has_glass = false;
-    c->planes_have_glass = c->triangles_have_glass = false;
-    for (int i = 0; i < n_spheres; ++i) c->has_glass |= spheres[i].brdf_tag == PTMI_GLASS;
-    for (int j = 0; j < n_planes; ++j) c->planes_have_glass |= planes[j].brdf_tag == PTMI_GLASS;
-    c->has_glass |= c->planes_have_glass;
-    c->fixed_has_glass = c->has_glass;
-    for (int k = 0; k < n_triangles; ++k) c->triangles_have_glass |= triangles[k].brdf_tag == PTMI_GLASS;
-    c->has_glass |= c->triangles_have_glass;
-    return PTMI_OK;
-#endif
-}
-
-// Moving the vertices of the current mesh scene (see include/ptmi.h).  One validation path, on the device: the check kernel reads the new
-// vertices only; the host reads its verdict and the new box back with the call's ONE synchronisation; only then are the writing kernels
-// enqueued -- into the second mesh block, which becomes the scene's when all of them are out.  c->mu is held.
-static int update_mesh_locked(ptmi_ctx *c, const float *d_vertices, int n_triangles)
-{
-    const int n = n_triangles;
-    unsigned int *result = c->d_refit.as<unsigned int>();
-    const int32_t *leaf_pos = reinterpret_cast<const int32_t *>(c->d_refit.as<char>() + c->refit_leaf_pos_at);
-    const int32_t *level_nodes = reinterpret_cast<const int32_t *>(c->d_refit.as<char>() + c->refit_levels_at);
-    unsigned int got[kRefitWords];
-    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kRefitHi * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(result + kRefitHi, 0, (kRefitWords - kRefitHi) * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, launch_mesh_refit_check(d_vertices, n, leaf_pos, result, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    if (got[kRefitError] != 0xffffffffu) {
-        const std::string who = "triangle " + std::to_string(got[kRefitError] >> 2);
-        switch (got[kRefitError] & 3u) {
-        case kRefitBadVertex: return fail(c, PTMI_EINVAL, who + ": a vertex is not finite: a box cannot bound it");
-        case kRefitBadNormal: return fail(c, PTMI_EINVAL, who + ": its edges, normal or normal^2 are not finite");
-        default:
-            return fail(c, PTMI_EINVAL, who + " had zero area when the scene was set and is in no leaf: it cannot gain area, set the scene again (ptmi_set_scene_mesh)");
-        }
-    }
-    float4 *shadow = c->d_mesh_shadow.as<float4>();
-    float4 *geom = shadow + c->mesh_nodes_f4, *by_index = geom + c->mesh_geom_f4 + c->mesh_index_f4;
-    PTMI_HIP(c, launch_mesh_refit_records(d_vertices, n, leaf_pos, by_index, geom, c->stream));
-    for (size_t lv = 0; lv + 1 < c->refit_level_first.size(); ++lv)
-        PTMI_HIP(c, launch_mesh_refit_level(shadow, geom, level_nodes + c->refit_level_first[lv], c->refit_level_first[lv + 1] - c->refit_level_first[lv], c->stream));
-    std::swap(c->d_mesh, c->d_mesh_shadow);
-    point_mesh_view(c);
-    for (int a = 0; a < 3; ++a) {
-        c->mesh.lo[a] = c->mesh.n_kept > 0 ? ordered_value(got[kRefitLo + a]) : 0.0f;
-        c->mesh.hi[a] = c->mesh.n_kept > 0 ? ordered_value(got[kRefitHi + a]) : 0.0f;
-    }
-    ++c->scene_version;
-    return PTMI_OK;
-}
-
-static int update_mesh_refusal(ptmi_ctx *c, const float *vertices, int n_triangles)
-{
-    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh): there are no vertices to move");
-    if (n_triangles != c->mesh.n_triangles)
-        return fail(c, PTMI_EINVAL, "the scene has " + std::to_string(c->mesh.n_triangles) + " triangles, not " + std::to_string(n_triangles) +
-                                        ": an update moves vertices, it does not change the topology");
-    if (n_triangles > 0 && !vertices) return fail(c, PTMI_EINVAL, "bad vertex arguments");
-    return PTMI_OK;
-}
-
-int ptmi_update_mesh_vertices_device(ptmi_ctx *c, const float *d_vertices, int n_triangles)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = update_mesh_refusal(c, d_vertices, n_triangles)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    return update_mesh_locked(c, d_vertices, n_triangles);
-}
-
-int ptmi_update_mesh_vertices(ptmi_ctx *c, const float *vertices, int n_triangles)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = update_mesh_refusal(c, vertices, n_triangles)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    if (n_triangles > 0) {
-        const size_t bytes = (size_t)n_triangles * 9 * sizeof(float);
-        if (int rc = grow(c, c->d_refit_staging, bytes, "vertex staging")) return rc;
-        CopySpan span{c->d_refit_staging.p, const_cast<float *>(vertices), bytes};
-        PTMI_HIP(c, copy_to_device(c, &span, 1));
-    }
-    return update_mesh_locked(c, c->d_refit_staging.as<float>(), n_triangles);
-}
-
-// New triangles for the current mesh scene (see include/ptmi.h).  The check kernel reads the new triangles only; the host reads its
-// verdict, the kept count, the box and the GLASS flag back together; then fresh blocks -- the scene block with the new material tail,
-// both mesh blocks, the refit's plan -- are filled on the stream and become the scene's when all of it is through: update_mesh_locked's
-// discipline with fresh allocations, the sizes change.  c->mu is held.
-static int set_mesh_triangles_locked(ptmi_ctx *c, const float *d_triangles, int n_triangles)
-{
-    const int n = n_triangles;
-    unsigned int *result = c->d_refit.as<unsigned int>();
-    unsigned int got[kBuildWords];
-    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kBuildHi * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(result + kBuildHi, 0, (kBuildWords - kBuildHi) * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, launch_mesh_build_check(d_triangles, n, result, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    if (got[kBuildError] != 0xffffffffu) {
-        const std::string who = "triangle " + std::to_string(got[kBuildError] >> 2);
-        switch (got[kBuildError] & 3u) {
-        case kBuildBadVertex: return fail(c, PTMI_EINVAL, who + ": a vertex is not finite: a box cannot bound it");
-        case kBuildBadMaterial: return fail(c, PTMI_EINVAL, who + ": its colour, illuminance or brdf_param is not finite");
-        case kBuildBadNormal: return fail(c, PTMI_EINVAL, who + ": its edges, normal or normal^2 are not finite");
-        default: return fail(c, PTMI_EINVAL, who + ": unknown brdf_tag");
-        }
-    }
-    if (got[kBuildKept] > (unsigned int)n) return fail(c, PTMI_EHIP, "the check kernel counted more kept triangles than there are");
-    const int kept = (int)got[kBuildKept];
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    if (kept > 0)
-        for (int a = 0; a < 3; ++a) { lo[a] = ordered_value(got[kBuildLo + a]); hi[a] = ordered_value(got[kBuildHi + a]); }
-    // the topology and its levels are functions of the kept count alone (ptmi_mesh_morton.h)
-    MeshBuild mb;
-    MeshRefitPlan plan;
-    morton_topology(kept, mb.nodes);
-    mesh_refit_plan(mb, 0, plan);
-    const size_t prefix_f4 = c->d_scene.bytes / sizeof(float4) - 2 * (size_t)c->mesh.n_triangles;      // spheres and planes, and their materials
-    const size_t tn_f4 = mb.nodes.size() * 4, tg_f4 = 3 * (size_t)kept, ti_f4 = ((size_t)kept + 3) / 4, tb_f4 = 3 * (size_t)n;
-    const size_t leaf_pos_at = 256, levels_at = leaf_pos_at + (((size_t)n * sizeof(int32_t) + 255) / 256) * 256;
-    DeviceBlock fresh, fresh_mesh, fresh_shadow, fresh_refit, sort;
-    auto undo = [&]() { release(fresh); release(fresh_mesh); release(fresh_shadow); release(fresh_refit); release(sort); };
-    hipError_t e = allocate(fresh, (prefix_f4 + 2 * (size_t)n) * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_mesh, (tn_f4 + tg_f4 + ti_f4 + tb_f4) * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_shadow, fresh_mesh.bytes);
-    if (e == hipSuccess) e = allocate(fresh_refit, levels_at + plan.level_nodes.size() * sizeof(int32_t));
-    if (e == hipSuccess && kept > 0) e = allocate(sort, mesh_build_sort_bytes(n));
-    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
-    float4 *nodes = fresh_mesh.as<float4>(), *geom = nodes + tn_f4, *by_index = geom + tg_f4 + ti_f4;
-    int32_t *order = reinterpret_cast<int32_t *>(geom + tg_f4);
-    int32_t *leaf_pos = reinterpret_cast<int32_t *>(fresh_refit.as<char>() + leaf_pos_at);
-    int32_t *level_nodes = reinterpret_cast<int32_t *>(fresh_refit.as<char>() + levels_at);
-    if (prefix_f4 > 0) e = hipMemcpyAsync(fresh.p, c->d_scene.p, prefix_f4 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) {
-        CopySpan spans[2] = {{nodes, mb.nodes.data(), mb.nodes.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
-        e = copy_to_device(c, spans, 2);
-    }
-    if (e == hipSuccess && n > 0) {
-        if (kept > 0) e = launch_mesh_build_order(d_triangles, n, kept, lo, hi, sort.p, leaf_pos, order, c->stream);
-        else e = hipMemsetAsync(leaf_pos, 0xff, (size_t)n * sizeof(int32_t), c->stream);                // no triangle is in a leaf
-    }
-    if (e == hipSuccess) e = launch_mesh_build_scatter(d_triangles, n, kept, leaf_pos, by_index, geom, fresh.as<float4>() + prefix_f4, c->stream);
-    for (size_t lv = 0; lv + 1 < plan.level_first.size() && e == hipSuccess; ++lv)
-        e = launch_mesh_refit_level(nodes, geom, level_nodes + plan.level_first[lv], plan.level_first[lv + 1] - plan.level_first[lv], c->stream);
-    // (the second block starts as a copy: an update rewrites every record and every box of it, the references and indices never move)
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh_shadow.p, fresh_mesh.p, fresh_mesh.bytes, hipMemcpyDeviceToDevice, c->stream);
-    // the stream is drained before the old blocks and the sort's scratch go (grow()'s rule), and a launch that failed on the device is
-    // seen while the old scene still stands; `mb` and `plan` die at return
-    const hipError_t drained = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = drained;
-    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
-    release(sort);
-    release(c->d_scene);
-    release(c->d_mesh);
-    release(c->d_mesh_shadow);
-    release(c->d_refit);
-    // (the second scene block of ptmi_update_spheres was a copy of the block that goes, with the old triangles' materials: the next
-    // update makes its pair afresh)
-    release(c->d_bvh_shadow);
-    release(c->d_scene_shadow);
-    c->d_scene = fresh;
-    c->d_mesh = fresh_mesh;
-    c->d_mesh_shadow = fresh_shadow;
-    c->d_refit = fresh_refit;
-    c->mesh_nodes_f4 = tn_f4; c->mesh_geom_f4 = tg_f4; c->mesh_index_f4 = ti_f4;
-    c->refit_leaf_pos_at = leaf_pos_at; c->refit_levels_at = levels_at;
-    c->refit_level_first = std::move(plan.level_first);
-    point_mesh_view(c);
-    c->mesh.n_triangles = n;
-    c->mesh.n_kept = kept;
-    for (int a = 0; a < 3; ++a) { c->mesh.lo[a] = lo[a]; c->mesh.hi[a] = hi[a]; }
-    c->triangles_have_glass = got[kBuildGlass] != 0;
-    c->has_glass = c->fixed_has_glass || c->triangles_have_glass;
-    ++c->scene_version;
-    return PTMI_OK;
-}
-
-static int set_mesh_triangles_refusal(ptmi_ctx *c, const void *triangles, int n_triangles)
-{
-    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh): there are no triangles to replace");
-    if (n_triangles < 0 || (n_triangles > 0 && !triangles)) return fail(c, PTMI_EINVAL, "bad triangle arguments");
-    if (n_triangles > PTMI_MAX_MESH_TRIANGLES) return fail(c, PTMI_ELIMIT, "more triangles than PTMI_MAX_MESH_TRIANGLES");
-    if (n_triangles == 0 && c->n_spheres + c->n_planes == 0) return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
-    return PTMI_OK;
-}
-
-int ptmi_set_mesh_triangles_device(ptmi_ctx *c, const ptmi_triangle *d_triangles, int n_triangles)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = set_mesh_triangles_refusal(c, d_triangles, n_triangles)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    return set_mesh_triangles_locked(c, reinterpret_cast<const float *>(d_triangles), n_triangles);
-}
-
-int ptmi_set_mesh_triangles(ptmi_ctx *c, const ptmi_triangle *triangles, int n_triangles)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = set_mesh_triangles_refusal(c, triangles, n_triangles)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    if (n_triangles > 0) {
-        const size_t bytes = (size_t)n_triangles * sizeof(ptmi_triangle);
-        if (int rc = grow(c, c->d_refit_staging, bytes, "triangle staging")) return rc;
-        CopySpan span{c->d_refit_staging.p, const_cast<ptmi_triangle *>(triangles), bytes};
-        PTMI_HIP(c, copy_to_device(c, &span, 1));
-    }
-    return set_mesh_triangles_locked(c, c->d_refit_staging.as<float>(), n_triangles);
-}
-
-int ptmi_mesh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, int32_t *order, int *n_kept)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (!c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a mesh scene (ptmi_set_scene_mesh)");
-    const size_t n_nodes = c->mesh_nodes_f4 / 4, kept = (size_t)c->mesh.n_kept;
-    if (!nodes && !order) {                                  // the sizes only
-        if (n_kept) *n_kept = (int)kept;
-        return (int)n_nodes;
-    }
-    if (!nodes || (kept > 0 && !order)) return fail(c, PTMI_EINVAL, "bad layout arguments");
-    if (node_capacity < 0 || (size_t)node_capacity < n_nodes) return fail(c, PTMI_ELIMIT, "node_capacity is smaller than the hierarchy");
-    PTMI_HIP(c, hipSetDevice(c->device));
-    CopySpan spans[2] = {{const_cast<float4 *>(c->mesh.nodes), nodes, n_nodes * sizeof(ptmi_bvh_node)},
-                         {const_cast<int *>(c->mesh.index), order, kept * sizeof(int32_t)}};
-    PTMI_HIP(c, copy_to_host(c, spans, 2));
-    if (n_kept) *n_kept = (int)kept;
-    return (int)n_nodes;
-}
-
-// Moving the spheres of the current BVH or mesh scene (see include/ptmi.h).  One validation path, on the device: the check kernel reads the
-// new geometry only; the host reads its verdict and the new box of the centres back with the call's ONE synchronisation; only then are
-// the writing kernels enqueued -- into the second hierarchy and scene blocks, which become the scene's when all of them are out.  c->mu is held.
-static int update_spheres_locked(ptmi_ctx *c, const float *d_geometry, int n)
-{
-    if (n == 0) return PTMI_OK;                            // (a scene without spheres: nothing moves)
-    unsigned int *result = c->d_bvh_plan.as<unsigned int>();
-    const int32_t *level_nodes = reinterpret_cast<const int32_t *>(c->d_bvh_plan.as<char>() + kBvhPlanLevelsAt);
-    unsigned int got[kSphWords];
-    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kSphHi * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(result + kSphHi, 0, (kSphWords - kSphHi) * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, launch_bvh_check(d_geometry, 4, n, result, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    if (got[kSphError] != 0xffffffffu)
-        return fail(c, PTMI_EINVAL, "sphere " + std::to_string(got[kSphError] >> 2) + ": its position, radius or radius^2 is not finite: a box cannot bound it");
-    if (c->d_bvh_shadow.bytes != c->d_bvh.bytes || c->d_scene_shadow.bytes != c->d_scene.bytes || !c->d_bvh_shadow.p || !c->d_scene_shadow.p) {
-        // (after the verdict: a refused update allocates nothing)  The second blocks start as copies of the scene's: an update rewrites
-        // every box, every sphere record and every sphere row of them; the references, the indices, the planes and the materials never
-        // move -- and whatever replaces d_scene or d_bvh releases the pair
-        release(c->d_bvh_shadow);
-        release(c->d_scene_shadow);
-        hipError_t e = allocate(c->d_bvh_shadow, c->d_bvh.bytes);
-        if (e == hipSuccess) e = allocate(c->d_scene_shadow, c->d_scene.bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_bvh_shadow.p, c->d_bvh.p, c->d_bvh.bytes, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_scene_shadow.p, c->d_scene.p, c->d_scene.bytes, hipMemcpyDeviceToDevice, c->stream);
-        if (e != hipSuccess) { release(c->d_bvh_shadow); release(c->d_scene_shadow); PTMI_HIP(c, e); }
-    }
-    float4 *shadow = c->d_bvh_shadow.as<float4>();
-    float4 *geom = shadow + c->bvh_nodes_f4;
-    const int32_t *order = reinterpret_cast<const int32_t *>(geom + (size_t)n);
-    PTMI_HIP(c, launch_bvh_records(d_geometry, 4, n, order, geom, c->d_scene_shadow.as<float4>(), nullptr, c->stream));
-    for (size_t lv = 0; lv + 1 < c->bvh_level_first.size(); ++lv)
-        PTMI_HIP(c, launch_bvh_level(shadow, d_geometry, 4, n, order, level_nodes + c->bvh_level_first[lv], c->bvh_level_first[lv + 1] - c->bvh_level_first[lv], c->stream));
-    std::swap(c->d_bvh, c->d_bvh_shadow);
-    std::swap(c->d_scene, c->d_scene_shadow);
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = ordered_value(got[kSphLo + a]); c->bvh.hi[a] = ordered_value(got[kSphHi + a]); }
-    point_bvh_view(c);
-    ++c->scene_version;
-    return PTMI_OK;
-}
-
-static int update_spheres_refusal(ptmi_ctx *c, const float *geometry, int n_spheres)
-{
-    if (!c->scene_bvh && !c->scene_mesh)
-        return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh): there is no hierarchy to refit");
-    if (n_spheres != c->n_spheres)
-        return fail(c, PTMI_EINVAL, "the scene has " + std::to_string(c->n_spheres) + " spheres, not " + std::to_string(n_spheres) +
-                                        ": an update moves spheres, it does not change their count (ptmi_set_bvh_spheres does)");
-    if (n_spheres > 0 && !geometry) return fail(c, PTMI_EINVAL, "bad sphere arguments");
-    return PTMI_OK;
-}
-
-int ptmi_update_spheres_device(ptmi_ctx *c, const float *d_geometry, int n_spheres)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = update_spheres_refusal(c, d_geometry, n_spheres)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    return update_spheres_locked(c, d_geometry, n_spheres);
-}
-
-int ptmi_update_spheres(ptmi_ctx *c, const float *geometry, int n_spheres)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = update_spheres_refusal(c, geometry, n_spheres)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    if (n_spheres > 0) {
-        const size_t bytes = (size_t)n_spheres * 4 * sizeof(float);
-        if (int rc = grow(c, c->d_sphere_staging, bytes, "sphere staging")) return rc;
-        CopySpan span{c->d_sphere_staging.p, const_cast<float *>(geometry), bytes};
-        PTMI_HIP(c, copy_to_device(c, &span, 1));
-    }
-    return update_spheres_locked(c, c->d_sphere_staging.as<float>(), n_spheres);
-}
-
-// New spheres for the current BVH or mesh scene (see include/ptmi.h).  The check kernel reads the new spheres only; the host reads its
-// verdict, the box of the centres and the GLASS flag back together (the first synchronisation); then fresh blocks -- the scene block for
-// the new count, the hierarchy, its plan -- are filled on the stream and become the scene's when all of it is through (the second).  Under
-// PTMI_BVH_BUILD_SPATIAL the topology is built on the device first and the counts of its levels are read back (one synchronisation more,
-// three in all).  c->mu is held.
-static int set_bvh_spheres_locked(ptmi_ctx *c, const float *d_spheres, int n)
-{
-    unsigned int *result = c->d_bvh_plan.as<unsigned int>();
-    unsigned int got[kSphWords];
-    PTMI_HIP(c, hipMemsetAsync(result, 0xff, kSphHi * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(result + kSphHi, 0, (kSphWords - kSphHi) * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, launch_bvh_check(d_spheres, 10, n, result, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    if (got[kSphError] != 0xffffffffu) {
-        const std::string who = "sphere " + std::to_string(got[kSphError] >> 2);
-        switch (got[kSphError] & 3u) {
-        case kSphBadGeometry: return fail(c, PTMI_EINVAL, who + ": its position, radius or radius^2 is not finite: a box cannot bound it");
-        case kSphBadMaterial: return fail(c, PTMI_EINVAL, who + ": its colour, illuminance or brdf_param is not finite");
-        default: return fail(c, PTMI_EINVAL, who + ": unknown brdf_tag");
-        }
-    }
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    if (n > 0)
-        for (int a = 0; a < 3; ++a) { lo[a] = ordered_value(got[kSphLo + a]); hi[a] = ordered_value(got[kSphHi + a]); }
-    const size_t old_ns = (size_t)c->n_spheres, np = (size_t)c->n_planes, nt = c->scene_mesh ? (size_t)c->mesh.n_triangles : 0, ns = (size_t)n;
-    const bool spatial = c->opt_bvh_build == PTMI_BVH_BUILD_SPATIAL;
-    std::vector<ptmi_bvh_node> topology;
-    BvhLevelPlan plan;
-    DeviceBlock fresh, fresh_bvh, fresh_plan, sort, work;
-    auto undo = [&]() { release(fresh); release(fresh_bvh); release(fresh_plan); release(sort); release(work); };
-    hipError_t e = hipSuccess;
-    size_t n_nodes = 0;
-    const uint32_t *sorted = nullptr;
-    int level_count[kSpatialWords] = {0};
-    int levels = 0;
-    if (!spatial) {
-        // the topology and its levels are functions of the count alone (ptmi_mesh_morton.h)
-        morton_topology(n, topology);
-        bvh_level_plan(topology, plan);
-        n_nodes = topology.size();
-    } else {
-        // the topology is the keys' (ptmi_bvh_spatial.h): built level by level into scratch, and the levels' counts read back -- this
-        // build's extra synchronisation -- before the hierarchy can be allocated
-        if (n > 0) e = allocate(sort, mesh_build_sort_bytes(n));
-        if (e == hipSuccess) e = allocate(work, bvh_spatial_work_bytes(n));
-        if (e == hipSuccess) e = launch_bvh_spatial_tree(d_spheres, n, lo, hi, sort.p, work.p, &sorted, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(level_count, bvh_spatial_report(work.p, n), sizeof level_count, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t read = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = read;
-        if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
-        // levels of 1, <= 2, <= 4 ... nodes, then none: anything else is not a tree this build makes
-        bool sane = level_count[0] == 1;
-        for (levels = 0; levels < PTMI_BVH_MAX_DEPTH && level_count[levels] > 0; ++levels) {
-            sane = sane && level_count[levels] <= spatial_level_bound(n, levels) && (levels == 0 || level_count[levels] <= 2 * level_count[levels - 1]);
-            n_nodes += (size_t)level_count[levels];
-        }
-        for (int l = levels; l < PTMI_BVH_MAX_DEPTH; ++l) sane = sane && level_count[l] == 0;
-        if (!sane || n_nodes > (size_t)spatial_node_bound(n)) {
-            undo();
-            return fail(c, PTMI_EHIP, "the device build of the sphere hierarchy reported levels that are no tree");
-        }
-        plan.level_first.assign(1, 0);
-        for (int l = levels - 1; l >= 0; --l) plan.level_first.push_back(plan.level_first.back() + level_count[l]);      // the deepest first
-    }
-    const size_t nodes_f4 = n_nodes * 4;
-    e = allocate(fresh, (ns + 2 * np + 2 * (ns + np) + 2 * nt) * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_bvh, (nodes_f4 + ns + (ns + 3) / 4) * sizeof(float4));
-    if (e == hipSuccess) e = allocate(fresh_plan, kBvhPlanLevelsAt + n_nodes * sizeof(int32_t));
-    if (e == hipSuccess && n > 0 && !spatial) e = allocate(sort, mesh_build_sort_bytes(n));
-    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
-    float4 *scene = fresh.as<float4>(), *nodes = fresh_bvh.as<float4>(), *geom = nodes + nodes_f4;
-    const float4 *old_scene = c->d_scene.as<float4>();
-    int32_t *order = reinterpret_cast<int32_t *>(geom + ns);
-    int32_t *level_nodes = reinterpret_cast<int32_t *>(fresh_plan.as<char>() + kBvhPlanLevelsAt);
-    // the planes' rows, and the materials of planes and triangles, move to the offsets of the new count
-    if (np > 0) e = hipMemcpyAsync(scene + ns, old_scene + old_ns, 2 * np * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess && np + nt > 0)
-        e = hipMemcpyAsync(scene + ns + 2 * np + 2 * ns, old_scene + old_ns + 2 * np + 2 * old_ns, 2 * (np + nt) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-    if (!spatial) {
-        if (e == hipSuccess) {
-            CopySpan spans[2] = {{nodes, topology.data(), topology.size() * sizeof(ptmi_bvh_node)}, {level_nodes, plan.level_nodes.data(), plan.level_nodes.size() * sizeof(int32_t)}};
-            e = copy_to_device(c, spans, 2);
-        }
-        if (e == hipSuccess) e = launch_bvh_build_order(d_spheres, n, lo, hi, sort.p, order, c->stream);
-    } else {
-        if (e == hipSuccess) e = launch_bvh_spatial_finish(work.p, n, level_count, levels, nodes, level_nodes, c->stream);
-        if (e == hipSuccess && n > 0) e = hipMemcpyAsync(order, sorted, ns * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);      // order[position] = original index
-    }
-    if (e == hipSuccess) e = launch_bvh_records(d_spheres, 10, n, order, geom, scene, scene + ns + 2 * np, c->stream);
-    for (size_t lv = 0; lv + 1 < plan.level_first.size() && e == hipSuccess; ++lv)
-        e = launch_bvh_level(nodes, d_spheres, 10, n, order, level_nodes + plan.level_first[lv], plan.level_first[lv + 1] - plan.level_first[lv], c->stream);
-    // the stream is drained before the old blocks and the sort's scratch go (grow()'s rule), and a launch that failed on the device is
-    // seen while the old scene still stands; `topology` and `plan` die at return
-    const hipError_t drained = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = drained;
-    if (e != hipSuccess) { undo(); PTMI_HIP(c, e); }
-    release(sort);
-    release(work);
-    release(c->d_scene);
-    release(c->d_bvh);
-    release(c->d_bvh_shadow);
-    release(c->d_scene_shadow);
-    release(c->d_bvh_plan);
-    c->d_scene = fresh;
-    c->d_bvh = fresh_bvh;
-    c->d_bvh_plan = fresh_plan;
-    c->bvh_nodes_f4 = nodes_f4;
-    c->bvh_level_first = std::move(plan.level_first);
-    c->n_spheres = n;
-    for (int a = 0; a < 3; ++a) { c->bvh.lo[a] = lo[a]; c->bvh.hi[a] = hi[a]; }
-    point_bvh_view(c);
-    c->fixed_has_glass = c->planes_have_glass || got[kSphGlass] != 0;
-    c->has_glass = c->fixed_has_glass || c->triangles_have_glass;
-    ++c->scene_version;
-    return PTMI_OK;
-}
-
-static int set_bvh_spheres_refusal(ptmi_ctx *c, const void *spheres, int n_spheres)
-{
-    if (!c->scene_bvh && !c->scene_mesh)
-        return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh): there are no spheres to replace");
-    if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(c, PTMI_EINVAL, "bad sphere arguments");
-    if (n_spheres > PTMI_MAX_BVH_SPHERES) return fail(c, PTMI_ELIMIT, "more spheres than PTMI_MAX_BVH_SPHERES");
-    if (n_spheres == 0 && c->n_planes == 0 && !(c->scene_mesh && c->mesh.n_triangles > 0))
-        return fail(c, PTMI_EINVAL, "empty scene (expMinWith on an empty list)");
-    return PTMI_OK;
-}
-
-int ptmi_set_bvh_spheres_device(ptmi_ctx *c, const ptmi_sphere *d_spheres, int n_spheres)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = set_bvh_spheres_refusal(c, d_spheres, n_spheres)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    return set_bvh_spheres_locked(c, reinterpret_cast<const float *>(d_spheres), n_spheres);
-}
-
-int ptmi_set_bvh_spheres(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (int rc = set_bvh_spheres_refusal(c, spheres, n_spheres)) return rc;
-    PTMI_HIP(c, hipSetDevice(c->device));
-    if (n_spheres > 0) {
-        const size_t bytes = (size_t)n_spheres * sizeof(ptmi_sphere);
-        if (int rc = grow(c, c->d_sphere_staging, bytes, "sphere staging")) return rc;
-        CopySpan span{c->d_sphere_staging.p, const_cast<ptmi_sphere *>(spheres), bytes};
-        PTMI_HIP(c, copy_to_device(c, &span, 1));
-    }
-    return set_bvh_spheres_locked(c, c->d_sphere_staging.as<float>(), n_spheres);
-}
-
-int ptmi_bvh_read_layout(ptmi_ctx *c, ptmi_bvh_node *nodes, int node_capacity, int32_t *order)
-{
-    if (!c) return PTMI_EINVAL;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (!c->scene_bvh && !c->scene_mesh) return fail(c, PTMI_ESTATE, "the current scene is not a BVH or mesh scene (ptmi_set_scene_bvh, ptmi_set_scene_mesh)");
-    const size_t n_nodes = c->bvh_nodes_f4 / 4, ns = (size_t)c->n_spheres;
-    if (!nodes && !order) return (int)n_nodes;               // the size only
-    if (!nodes) return fail(c, PTMI_EINVAL, "bad layout arguments");
-    if (node_capacity < 0 || (size_t)node_capacity < n_nodes) return fail(c, PTMI_ELIMIT, "node_capacity is smaller than the hierarchy");
-    PTMI_HIP(c, hipSetDevice(c->device));
-    CopySpan spans[2] = {{const_cast<float4 *>(c->bvh.nodes), nodes, n_nodes * sizeof(ptmi_bvh_node)},
-                         {const_cast<int *>(c->bvh.index), order, order ? ns * sizeof(int32_t) : 0}};      // (no order: the nodes alone)
-    PTMI_HIP(c, copy_to_host(c, spans, 2));
-    return (int)n_nodes;
-}
-
 int ptmi_set_partition(ptmi_ctx *c, int stripe_rows, int n_parts, int part)
 {
     if (!c) return PTMI_EINVAL;
@@ -2127,8 +1174,8 @@ int ptmi_set_variant(ptmi_ctx *c, int variant)
     std::lock_guard<std::mutex> lock(c->mu);
     if (variant < 0 || variant >= kVariantCount) return fail(c, PTMI_EINVAL, "unknown variant");
     if (!variant_available(variant)) return fail(c, PTMI_EINVAL, "this variant is an ablation kernel: build libptmi with -DPTMI_ABLATIONS");
-    if (c->scene_bvh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
-    if (c->scene_mesh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels only (variant 0)");
+    if (c->scene.kind == SceneKind::Bvh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
+    if (c->scene.kind == SceneKind::Mesh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels only (variant 0)");
     c->variant = variant;
     return PTMI_OK;
 }
@@ -2189,8 +1236,8 @@ int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
         return PTMI_OK;
     case PTMI_OPT_STREAMS_FORM:
         if (value != PTMI_FORM_AUTO && value != PTMI_FORM_STREAM && value != PTMI_FORM_PIXEL) return fail(c, PTMI_EINVAL, "unknown Streams form");
-        if (c->scene_bvh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a BVH scene has no stream form (PTMI_FORM_STREAM)");
-        if (c->scene_mesh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a mesh scene has no stream form (PTMI_FORM_STREAM)");
+        if (c->scene.kind == SceneKind::Bvh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a BVH scene has no stream form (PTMI_FORM_STREAM)");
+        if (c->scene.kind == SceneKind::Mesh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a mesh scene has no stream form (PTMI_FORM_STREAM)");
         c->opt_form = (int)value; return PTMI_OK;
     case PTMI_OPT_STREAM_BATCH:
         if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "stream batch must be in [0, 64] samples");
@@ -2356,7 +1403,7 @@ int ptmi_render_blocks(ptmi_ctx *c, int algorithm)
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
     const bool stream_form = uses_stream_form(c, algorithm, c->n_parts, -1);        // (for some sample count: the automatic choice looks at it)
-    const bool ordered = !c->has_glass && (c->opt_batch == 0 || effective_seed_rule(c) == PTMI_SEED_FROM_RESULT);
+    const bool ordered = !c->scene.has_glass && (c->opt_batch == 0 || effective_seed_rule(c) == PTMI_SEED_FROM_RESULT);
     return stream_form && !ordered ? 1 : 0;
 }
 
@@ -2662,7 +1709,7 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
     if (n < 0 || (n > 0 && (!rays || !t_out || !idx_out || !just_out))) return fail(c, PTMI_EINVAL, "bad point-query arguments");
-    if (!c->d_scene.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     if (n == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
     const size_t nb = (size_t)n;
@@ -2673,9 +1720,9 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     PTMI_HIP(c, hipMemcpyAsync(d_rays, rays, nb * 6 * 4, hipMemcpyHostToDevice, c->stream));
     SceneView scene;
-    scene.packed = c->d_scene.as<float4>(); scene.n_spheres = c->n_spheres; scene.n_planes = c->n_planes;
-    if (c->scene_mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(scene, c->mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
-    else PTMI_HIP(c, launch_eval_check_hit(scene, c->scene_bvh ? &c->bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
+    scene.packed = c->scene.packed.as<float4>(); scene.n_spheres = (int)c->scene.rows.ns; scene.n_planes = (int)c->scene.rows.np;
+    if (c->scene.kind == SceneKind::Mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(scene, c->scene.mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
+    else PTMI_HIP(c, launch_eval_check_hit(scene, c->scene.kind == SceneKind::Bvh ? &c->scene.bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(t_out, d_t, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(idx_out, d_idx, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(just_out, d_just, nb * 4, hipMemcpyDeviceToHost, c->stream));

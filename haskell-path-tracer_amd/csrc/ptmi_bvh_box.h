@@ -64,7 +64,7 @@ PTMI_HD void bvh_empty_child(float center[3], float half[3], float &inv_2r)
     inv_2r = 0.0f;
 }
 
-// What the first kernel of ptmi_update_spheres / ptmi_set_bvh_spheres reports (ptmi_bvh_refit.hip, ptmi_bvh_build.hip -> ptmi_api.cpp),
+// What the first kernel of ptmi_update_spheres / ptmi_set_bvh_spheres reports (ptmi_bvh_refit.hip, ptmi_bvh_build.hip -> ptmi_scene.cpp),
 // in the mesh calls' form: result[kSphError] = the smallest (sphere << 2 | code) of a refused sphere, all ones when there is none; the box
 // of the CENTRES as order-preserving integer images (ordered_image); whether any sphere is GLASS.  All ones in [0, kSphHi), zero behind,
 // at launch.

@@ -78,7 +78,7 @@ PTMI_HD int spatial_split(const uint64_t *key, int b, int e, int level, int *fal
 // the reference to the leaf of positions [b, e) of the leaf order (-1: an empty child)
 PTMI_HD int32_t spatial_leaf_ref(int b, int e) { return e == b ? -1 : -1 - (int32_t)(((uint32_t)b << 8) | (uint32_t)(e - b)); }
 
-// What the device build reports to the host (ptmi_bvh_lbvh.hip -> ptmi_api.cpp): the number of nodes of every level, 0 ..
+// What the device build reports to the host (ptmi_bvh_lbvh.hip -> ptmi_scene.cpp): the number of nodes of every level, 0 ..
 // PTMI_BVH_MAX_DEPTH - 1, and how many nodes took the equal-count split.
 enum { kSpatialFallbacks = PTMI_BVH_MAX_DEPTH, kSpatialWords = PTMI_BVH_MAX_DEPTH + 1 };
 

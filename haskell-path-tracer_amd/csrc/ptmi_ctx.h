@@ -1,0 +1,251 @@
+// ptmi_ctx.h -- what the host units of the C ABI share: the context, its device blocks and the scene's device state (internal; ptmi_api.cpp
+// renders, ptmi_scene.cpp sets, moves and replaces geometry).
+#pragma once
+
+#include "../../include/ptmi.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ptmi_kernels.h"
+#include "ptmi_stage.h"
+
+// A device block of the context: null <=> 0 bytes.  grow() and release() below keep that, and that nothing the stream may still read is freed.
+struct DeviceBlock {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+namespace ptmi {
+
+// ---- the layouts of the scene's blocks: each a function of its counts, used by whoever fills a block and whoever points into it ----
+// The packed scene, in float4 rows: spheres | planes (two rows each) | materials of spheres, planes and -- a mesh scene -- triangles (two rows each)
+struct PackedRows {
+    size_t ns = 0, np = 0, nt = 0;
+    size_t planes_at() const { return ns; }
+    size_t materials_at() const { return ns + 2 * np; }
+    size_t kept_materials_at() const { return materials_at() + 2 * ns; }            // planes', then triangles': what new spheres keep
+    size_t triangle_materials_at() const { return materials_at() + 2 * (ns + np); }
+    size_t rows() const { return triangle_materials_at() + 2 * nt; }
+    size_t bytes() const { return rows() * sizeof(float4); }
+};
+// The sphere hierarchy, in float4: nodes (four each) | spheres in leaf order | their original indices
+struct SphereLayout {
+    size_t n_nodes = 0, ns = 0;
+    size_t geom_at() const { return 4 * n_nodes; }
+    size_t index_at() const { return geom_at() + ns; }
+    size_t bytes() const { return (index_at() + (ns + 3) / 4) * sizeof(float4); }
+};
+// The triangle hierarchy, in float4: nodes | kept records in leaf order (three each) | their original indices | every record by index
+struct MeshLayout {
+    size_t n_nodes = 0, kept = 0, nt = 0;
+    size_t geom_at() const { return 4 * n_nodes; }
+    size_t index_at() const { return geom_at() + 3 * kept; }
+    size_t by_index_at() const { return index_at() + (kept + 3) / 4; }
+    size_t bytes() const { return (by_index_at() + 3 * nt) * sizeof(float4); }
+};
+// A hierarchy's plan block, in bytes: a check kernel's result words | the primitives' leaf positions (the triangles' only) | the nodes level by level
+struct PlanLayout {
+    size_t n_leaf_pos = 0, n_nodes = 0;
+    static constexpr size_t leaf_pos_at() { return 256; }
+    size_t levels_at() const { return leaf_pos_at() + ((n_leaf_pos * sizeof(int32_t) + 255) / 256) * 256; }
+    size_t bytes() const { return levels_at() + n_nodes * sizeof(int32_t); }
+};
+
+// One hierarchy of the scene: `block` is rendered from; a refit writes `shadow` (a block of the same layout) and swaps the two; `plan` holds what
+// the device calls need of the topology; `staging` the staged input of the host-pointer entries.
+template <class Layout> struct Hierarchy {
+    DeviceBlock block, shadow, plan, staging;
+    Layout layout;
+    PlanLayout plan_layout;
+    std::vector<int32_t> level_first;                      // launches + 1 offsets into the plan's nodes, the deepest level first
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    void set_box(const float *l, const float *h) { std::memcpy(lo, l, sizeof lo); std::memcpy(hi, h, sizeof hi); }
+    unsigned int *result() const { return plan.as<unsigned int>(); }
+    int32_t *leaf_pos() const { return reinterpret_cast<int32_t *>(plan.as<char>() + PlanLayout::leaf_pos_at()); }
+    int32_t *level_nodes() const { return reinterpret_cast<int32_t *>(plan.as<char>() + plan_layout.levels_at()); }
+};
+
+enum class SceneKind { Linear, Bvh, Mesh };
+
+// The scene's device state.  Only commit() (ptmi_scene.cpp) installs into it; everybody else reads.
+struct SceneState {
+    SceneKind kind = SceneKind::Linear;
+    DeviceBlock packed, packed_shadow;                     // PackedRows; the second block is the sphere refit's, beside spheres.shadow
+    PackedRows rows;
+    Hierarchy<SphereLayout> spheres;                       // a BVH or mesh scene
+    Hierarchy<MeshLayout> triangles;                       // a mesh scene
+    bool glass_spheres = false, glass_planes = false, glass_triangles = false;
+    bool has_glass = false;                                // any of the three (commit)
+    BvhView bvh{};                                         // into spheres.block
+    MeshView mesh{};                                       // into triangles.block (and a copy of bvh)
+    uint64_t version = 0;                                  // bumped by every commit: the order's and the start-hit list's key
+    bool hierarchical() const { return kind != SceneKind::Linear; }
+    template <class F> void each_block(F &&f)
+    {
+        for (DeviceBlock *b : {&packed, &packed_shadow, &spheres.block, &spheres.shadow, &spheres.plan, &spheres.staging,
+                               &triangles.block, &triangles.shadow, &triangles.plan, &triangles.staging})
+            f(*b);
+    }
+};
+
+}  // namespace ptmi
+
+struct ptmi_ctx {
+    std::mutex mu;
+    int device = 0;
+    std::string err;
+
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+
+    int width = 0, height = 0;
+    int stripe_rows = 0, n_parts = 1, part = 0;   // stripe_rows == 0: one part holds everything
+    int rows_local = 0;
+
+    ptmi::Planes owned{};          // seven planes carved from owned_block
+    DeviceBlock owned_block;
+    ptmi::Planes bound{};
+    bool use_bound = false;
+
+    ptmi::SceneState scene;  // what is rendered (ptmi_scene.cpp)
+    int opt_bvh_build = PTMI_BVH_BUILD_EQUAL_COUNT;   // PTMI_OPT_BVH_DEVICE_BUILD: which tree ptmi_set_bvh_spheres builds
+
+    DeviceBlock d_live;      // unsigned long long
+    DeviceBlock d_work;      // unsigned int
+    DeviceBlock d_iters;     // unsigned int
+    uint64_t nominal = 0, samples = 0;
+
+    bool timing = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_snap = nullptr;
+    // The stream form's tail (render_streams_wavefront): the end of the dispatch order is rendered by the per-pixel kernel on a
+    // stream of its own, beside the persistent launch.  d_tail_start: where that end begins (written by the order kernel).
+    hipStream_t tail_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DeviceBlock d_tail_start;   // unsigned int
+    int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
+    bool ev_valid = false;
+    int variant = ptmi::kVariantAuto;
+    ptmi::Stager stager;                          // pinned ring + worker threads for host-buffer entry points (ptmi_stage.h)
+
+    // cost-ordered dispatch of the tiled kernels: what every quad of tiles cost in the last launch with this key, and
+    // the order (most expensive first) later launches with the same key use.  order_state = launches made with this key
+    DeviceBlock d_quad_cost, d_quad_order, d_quad_class;   // unsigned int per quad
+    int order_state = 0;
+    DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup
+    unsigned int chunk_capacity = 0;           // ... that many (the ticket counter's line follows)
+    struct OrderKey { ptmi_camera cam; uint64_t scene_version; int dims[8]; } order_key{};
+
+    // scratch for ptmi_render1 / point queries
+    DeviceBlock scratch;
+
+    // wavefront Streams (scenes with the GLASS extension): two ray streams + {next length, dropped}
+    DeviceBlock queue_block;
+    size_t queue_capacity = 0;       // ... rays per stream
+    DeviceBlock hit_block;           // stream form: the start hits of the pixels, in regions (HitList)
+    size_t hit_capacity = 0;         // ... slots
+    DeviceBlock d_hit_counts;        // ... records per region (unsigned int)
+    DeviceBlock d_hit_missed;        // ... and the pixels of every region that have none (unsigned long long)
+    unsigned int hit_regions = 0;
+    // The start-hit list is a function of (camera, scene, shape, partition, dispatch order) only -- every sample of a pixel
+    // shoots the same primary ray, in every call -- so it is kept until one of them changes.
+    struct HitKey { ptmi_camera cam; uint64_t scene_version, order_generation; int dims[8]; unsigned int region_slots; int cap_allows_split; const void *planes_r; } hit_key{};
+    bool hit_list_valid = false;
+    uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
+    uint64_t hit_split_pixels = 0;          // pixels whose glass primary hit the list replaced by its children's hits
+    DeviceBlock d_snapshots;         // stream form, split kernel: the seed every item starts from
+    int cus = 0;                     // compute units of the device (persistent grids)
+    size_t device_memory = (size_t)64 << 30;   // bytes of the device (budget of the stream form's seed snapshots)
+    DeviceBlock tree_stack;          // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
+    DeviceBlock d_region_done;       // stream form, ordered passes: items published per region (unsigned int)
+    int opt_ordered_passes = 0;      // PTMI_OPT_ORDERED_PASSES: 0 = automatic, 1 = off, k = k passes
+    int opt_pass_handoff = 0;        // PTMI_OPT_PASS_HANDOFF: 0 = release / acquire once per (region, pass); 1 = the fence-free write-through hand-off
+    DeviceBlock d_pass_first;        // stream form, split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
+    std::vector<int> pass_first_host;   // ... what the device block holds
+    DeviceBlock d_qcount;            // stream form: kLvWords counter words (unsigned int)
+    uint64_t rays_dropped = 0;
+    uint64_t rays_truncated = 0;
+    uint64_t rays_spilled = 0;       // stream form: children that found the wave's ring full and went through HBM
+    uint64_t rays_overflowed = 0;    // ... and its spill queue too: traced by an overflow level
+    DeviceBlock spill_block;         // stream form: the waves' spill queues
+    uint64_t live_host = 0;        // live rays counted on the host (wavefront path)
+    DeviceBlock d_stream_counters;   // kScWords device counters of the per-pixel Streams kernels
+
+    // options of render Streams (ptmi_set_option)
+    int opt_seed_rule = PTMI_SEED_AUTO;              // resolved per scene: effective_seed_rule()
+    int opt_step_cap = ptmi::kStreamStepCapDefault;
+    int opt_capacity = 4;
+    int grown_capacity = 0;                          // stream form with GLASS: rays per pixel the overflow streams have been GROWN to after a call would have dropped children (0: never)
+    DeviceBlock colour_backup;                       // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
+    int opt_form = PTMI_FORM_AUTO;
+    int opt_batch = 0;
+    int opt_spp_chunks = 0;                    // 0 = automatic
+    int opt_arithmetic = PTMI_ARITH_EXACT;
+    int opt_glass_batch = 0;                   // PTMI_OPT_GLASS_BATCH: 0 = automatic, 1 = off, k = GLASS hits wait until k are pending in their wave
+    int opt_graded = 1;                        // PTMI_OPT_STREAM_GRADED: the split kernel's passes shrink towards the end of the launch
+    int opt_snapshot_mb = 0;                   // PTMI_OPT_SNAPSHOT_BUDGET_MB: 0 = an eighth of the device's memory
+    int opt_pass_groups = 0;                  // PTMI_OPT_STREAM_PASS_GROUPS: 0 = automatic, 1 = off, k = the last k passes are handed out region by region
+
+    // The chained closure (ptmi_render1_chained): the RenderResults the caller holds tokens for.  A state's seven planes are one device
+    // block (carve), or -- once it had to make room -- one host block of the same layout.  Blocks of released states wait in chain_free.
+    struct ChainState {
+        uint64_t token = 0;
+        int width = 0, height = 0;
+        void *block = nullptr;                 // device
+        std::unique_ptr<char[]> host;          // evicted: planes_bytes(n) bytes, carve's layout
+    };
+    std::vector<ChainState> chain;             // in token order (oldest first)
+    std::vector<std::pair<size_t, void *>> chain_free;   // (bytes, device block)
+    uint64_t chain_serial = 0;                 // this context's number in the process: the upper bits of its tokens
+    uint64_t chain_counter = 0;
+    int opt_chain_slots = 0;                   // PTMI_OPT_CHAIN_SLOTS: 0 = automatic
+    ptmi_chain_stats chain_stats{};
+
+    // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
+    template <class F> void each_block(F &&f)
+    {
+        for (DeviceBlock *b : {&owned_block, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
+                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
+                               &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
+            f(*b);
+        scene.each_block(f);
+    }
+};
+
+namespace ptmi {
+
+// The message of a failed call, and its code (the context's mutex is held by every caller with a context).
+int fail(ptmi_ctx *c, int code, const std::string &msg);
+
+// A runtime error leaves through this library's return code -- and not, a second time, through the runtime's sticky slot (hipGetLastError
+// keeps the last failure of the thread until somebody asks: the caller's next launch check, or another library's, would find it there).
+int fail_hip(ptmi_ctx *c, hipError_t e, const char *call);
+#define PTMI_HIP(c, call)                                                                  \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) return ptmi::fail_hip((c), e_, #call);                       \
+    } while (0)
+
+// The one allocation of a DeviceBlock (which must be empty).  On failure it stays empty and the runtime's sticky slot is cleared.
+hipError_t allocate(DeviceBlock &b, size_t bytes);
+void release(DeviceBlock &b);
+// `b` holds at least `bytes` (its contents are not kept).  A block that is replaced goes only once the stream is drained; with none
+// held nothing on the stream can read it (the tail stream has joined c->stream before any call returns).  If the allocation fails the
+// block is empty.
+int grow(ptmi_ctx *c, DeviceBlock &b, size_t bytes, const char *what);
+
+// Host-buffer transfers of the boundary (stream-ordered on c->stream).  Transfers of a megabyte or more go through
+// the context's Stager (ptmi_stage.h: parallel page copies into a pinned ring, one DMA per 8-MB chunk -- the driver
+// never pins the caller's pages); small ones, or all of them when the engine is off (PTMI_STAGE_THREADS=0), are
+// plain async copies.  copy_to_host leaves the stream drained in both cases.
+hipError_t copy_to_device(ptmi_ctx *c, const CopySpan *spans, int n);
+hipError_t copy_to_host(ptmi_ctx *c, const CopySpan *spans, int n);
+
+}  // namespace ptmi

@@ -1,4 +1,4 @@
-// ptmi_kernels.h -- launch interface between the C ABI (ptmi_api.cpp) and the gfx950 kernels (ptmi_*.hip, one unit per kernel family).
+// ptmi_kernels.h -- launch interface between the C ABI (ptmi_api.cpp, ptmi_scene.cpp) and the gfx950 kernels (ptmi_*.hip, one unit per kernel family).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,7 +17,7 @@ namespace ptmi {
 // (between the C ABI's two units: the image size a context stands at, 0 x 0 while it is unsized -- ptmi_group.cpp checks its members with it)
 void context_size(const ptmi_ctx *ctx, int *width, int *height);
 
-// Scene as staged into LDS, one float4 stream (see pack_scene in ptmi_api.cpp):
+// Scene as staged into LDS, one float4 stream (see pack_scene in ptmi_scene.cpp):
 //   [0, ns)                 sphere geometry   (cx, cy, cz, r*r)
 //   [ns, ns + 2 np)         plane geometry    (px, py, pz, 0) (nx, ny, nz, 0)
 //   [geom, geom + 2 (ns+np)) material         (cr, cg, cb, illuminance) (tag bits, p, p/pi, (1-p)/2)

@@ -91,7 +91,7 @@ PTMI_HD TriangleNormal triangle_normal(const float v0[3], const float v1[3], con
     return r;
 }
 
-// What the refit's first kernel reports (ptmi_mesh_refit.hip -> ptmi_api.cpp): result[kRefitError] = the smallest (triangle << 2 | code)
+// What the refit's first kernel reports (ptmi_mesh_refit.hip -> ptmi_scene.cpp): result[kRefitError] = the smallest (triangle << 2 | code)
 // of a refused triangle, all ones when there is none; the box of the leaf triangles' vertices as order-preserving integer images.
 enum { kRefitError = 0, kRefitLo = 1, kRefitHi = 4, kRefitWords = 8 };
 enum { kRefitBadVertex = 0, kRefitBadNormal = 1, kRefitGainsArea = 2 };

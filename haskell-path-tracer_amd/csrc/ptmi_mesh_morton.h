@@ -51,7 +51,7 @@ PTMI_HD uint64_t morton_key(const float v0[3], const float v1[3], const float v2
            morton_spread(morton_axis(v0[2], v1[2], v2[2], lo[2], hi[2]));
 }
 
-// What the build's first kernel reports (ptmi_mesh_build.hip -> ptmi_api.cpp), in the refit's form (ptmi_mesh_box.h): the smallest
+// What the build's first kernel reports (ptmi_mesh_build.hip -> ptmi_scene.cpp), in the refit's form (ptmi_mesh_box.h): the smallest
 // (triangle << 2 | code) of a refused triangle, all ones when there is none; the box of the kept triangles' vertices as ordered images;
 // how many triangles are kept; whether any is GLASS.  All ones in [0, kBuildHi), zero behind, at launch.
 enum { kBuildError = 0, kBuildLo = 1, kBuildHi = 4, kBuildKept = 7, kBuildGlass = 8, kBuildWords = 12 };

@@ -1,8 +1,9 @@
-// bvh_update_hostsan.cpp -- the host side of ptmi_update_spheres / ptmi_set_bvh_spheres under AddressSanitizer + UBSan, as a stand-alone
+// bvh_update_hostsan.cpp -- the host side of the scene's calls (csrc/ptmi_scene.cpp) under AddressSanitizer + UBSan, as a stand-alone
 // program: linked against the library built with its host code instrumented and against the HIP stand-in (tests/cxx/hip_stub.cpp:
 // device memory is host memory, kernels do not run), run directly by tests/test_bvh_update_host_sanitized.py.  It sets a BVH scene and a
 // mesh scene, updates from host and from stand-in device memory, sets new spheres with another count, provokes every refusal, and lets
-// every runtime call of the two new calls fail in turn; after each failure the layout read back is the one before the call.
+// every runtime call of ptmi_update_spheres, ptmi_set_bvh_spheres, ptmi_set_scene_bvh, ptmi_set_scene_mesh, ptmi_update_mesh_vertices and
+// ptmi_set_mesh_triangles (host and device entries) fail in turn; after each failure the layouts read back are the ones before the call.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,13 +50,16 @@ std::vector<float> geometry_of(const std::vector<ptmi_sphere> &s)
     return g;
 }
 
+// the sphere hierarchy, and -- a mesh scene -- the triangle hierarchy (t_nodes < 0: there is none)
 struct Layout {
-    int n_nodes = 0;
-    std::vector<ptmi_bvh_node> nodes;
-    std::vector<int32_t> order;
+    int n_nodes = 0, t_nodes = -1, kept = 0;
+    std::vector<ptmi_bvh_node> nodes, t_node;
+    std::vector<int32_t> order, t_order;
     bool operator==(const Layout &o) const
     {
-        return n_nodes == o.n_nodes && order == o.order && std::memcmp(nodes.data(), o.nodes.data(), nodes.size() * sizeof(ptmi_bvh_node)) == 0;
+        return n_nodes == o.n_nodes && order == o.order && std::memcmp(nodes.data(), o.nodes.data(), nodes.size() * sizeof(ptmi_bvh_node)) == 0 &&
+               t_nodes == o.t_nodes && kept == o.kept && t_order == o.t_order &&
+               (t_node.empty() || std::memcmp(t_node.data(), o.t_node.data(), t_node.size() * sizeof(ptmi_bvh_node)) == 0);
     }
 };
 
@@ -67,20 +71,27 @@ Layout read_layout(ptmi_ctx *c, int n_spheres)
     l.nodes.resize((size_t)l.n_nodes);
     l.order.resize((size_t)n_spheres);
     CHECK(ptmi_bvh_read_layout(c, l.nodes.data(), l.n_nodes, n_spheres ? l.order.data() : nullptr) == l.n_nodes);
+    l.t_nodes = ptmi_mesh_read_layout(c, nullptr, 0, nullptr, &l.kept);
+    if (l.t_nodes >= 0) {
+        l.t_node.resize((size_t)l.t_nodes);
+        l.t_order.resize((size_t)l.kept + 1);
+        CHECK(ptmi_mesh_read_layout(c, l.t_node.data(), l.t_nodes, l.t_order.data(), &l.kept) == l.t_nodes);
+    } else CHECK(l.t_nodes == PTMI_ESTATE);
     return l;
 }
 
 // `call` with the k-th runtime call of every kind failing, k = 1, 2, ... until the call gets through: each failure is PTMI_EHIP or
 // PTMI_ENOMEM and leaves the layout of `n_before` spheres as it was; `restore` brings that state back after a call that got through.
-// Returns how many failures were injected.
-template <class F, class R> int walk_failures(ptmi_ctx *c, int n_before, F &&call, R &&restore)
+// Returns how many failures were injected.  `same_blocks`: a failed call leaves as many live device blocks as it found (for calls whose staging
+// block, if any, stands already).
+template <class F, class R> int walk_failures(ptmi_ctx *c, int n_before, F &&call, R &&restore, bool same_blocks = false)
 {
     int injected = 0;
     for (int kind = 0; kind < 4; ++kind)
         for (long k = 1;; ++k) {
             const Layout before = read_layout(c, n_before);
             hipstub_fail(kind, k);
-            const long calls = hipstub_calls(kind);
+            const long calls = hipstub_calls(kind), live = hipstub_live_blocks();
             const int rc = call();
             const bool hit = hipstub_calls(kind) - calls >= k;
             hipstub_fail(kind, 0);
@@ -89,6 +100,7 @@ template <class F, class R> int walk_failures(ptmi_ctx *c, int n_before, F &&cal
             CHECK(rc == PTMI_EHIP || rc == PTMI_ENOMEM);
             CHECK(ptmi_last_error(c) && *ptmi_last_error(c));
             CHECK(read_layout(c, n_before) == before);
+            if (same_blocks) CHECK(hipstub_live_blocks() == live);
             ++injected;
         }
     return injected;
@@ -143,9 +155,21 @@ void scenario(bool mesh)
     }
     CHECK(read_layout(c, n) == as_set);
 
+    // a whole new scene of either kind over the one that stands, each with every runtime call failing in turn: the old scene stays whole
+    std::vector<ptmi_triangle> many40(40), few7(7);
+    for (size_t k = 0; k < many40.size(); ++k) { many40[k] = tri[k % 2]; many40[k].v0[2] -= (float)k; many40[k].v1[2] -= (float)k; many40[k].v2[2] -= (float)k; }
+    for (size_t k = 0; k < few7.size(); ++k) few7[k] = many40[3 * k];
+    auto set_again = [&] { return mesh ? ptmi_set_scene_mesh(c, s.data(), n, tri, 2, &plane, 1) : ptmi_set_scene_bvh(c, s.data(), n, &plane, 1); };
+    auto set_more_bvh = [&] { return ptmi_set_scene_bvh(c, more.data(), n2, &plane, 1); };
+    int injected = walk_failures(c, n, set_more_bvh, set_again, true);
+    injected += walk_failures(c, n2, [&] { return ptmi_set_scene_mesh(c, s.data(), n, many40.data(), 40, &plane, 1); }, set_more_bvh, true);
+    CHECK(read_layout(c, n).t_nodes >= 1);
+    CHECK(set_again() == PTMI_OK);
+    CHECK(read_layout(c, n) == as_set);
+
     // updates from host memory and from (stand-in) device memory, each with every runtime call failing in turn
     auto nothing = [] { return (int)PTMI_OK; };
-    int injected = walk_failures(c, n, [&] { return ptmi_update_spheres(c, g.data(), n); }, nothing);
+    injected += walk_failures(c, n, [&] { return ptmi_update_spheres(c, g.data(), n); }, nothing);
     void *d_g = nullptr;
     CHECK(hipMalloc(&d_g, g.size() * sizeof(float)) == hipSuccess);
     std::memcpy(d_g, g.data(), g.size() * sizeof(float));
@@ -184,6 +208,37 @@ void scenario(bool mesh)
         CHECK(ptmi_update_spheres(c, g.data(), n) == PTMI_OK);
         CHECK(ptmi_set_bvh_spheres(c, more.data(), n2) == PTMI_OK);                 // (copies the materials of planes and triangles out of the scene block)
         CHECK(ptmi_set_bvh_spheres(c, s.data(), n) == PTMI_OK);
+
+        // new triangles of another count, from host and stand-in device memory, with every runtime call failing in turn.  Kernels do not
+        // run: the check kernel's kept count is placed into its read-back, so that the sort, the scatter and every level are launched
+        void *d_t = nullptr;
+        CHECK(hipMalloc(&d_t, many40.size() * sizeof(ptmi_triangle)) == hipSuccess);
+        std::memcpy(d_t, many40.data(), many40.size() * sizeof(ptmi_triangle));
+        auto set_triangles = [&](const ptmi_triangle *t, int count, bool device) {
+            hipstub_poke("mesh_build_check_kernel", 1, 7 * sizeof(unsigned int), (unsigned int)count);   // (kBuildKept: all of them have area)
+            const int rc = device ? ptmi_set_mesh_triangles_device(c, t, count) : ptmi_set_mesh_triangles(c, t, count);
+            hipstub_clear_pokes();
+            return rc;
+        };
+        CHECK(set_triangles(many40.data(), 40, false) == PTMI_OK);                  // (the staging block stands from here on)
+        CHECK(read_layout(c, n).kept == 40);
+        injected += walk_failures(c, n, [&] { return set_triangles(few7.data(), 7, false); }, [&] { return set_triangles(many40.data(), 40, false); }, true);
+        CHECK(read_layout(c, n).kept == 7);
+        injected += walk_failures(c, n, [&] { return set_triangles(static_cast<const ptmi_triangle *>(d_t), 40, true); }, [&] { return set_triangles(few7.data(), 7, false); }, true);
+        const Layout forty = read_layout(c, n);
+        CHECK(forty.kept == 40 && forty.t_nodes > 7);                                // (several levels)
+        // ... and their vertices moved, over the plan the device call made
+        std::vector<float> v(40 * 9);
+        for (size_t k = 0; k < many40.size(); ++k) { std::memcpy(&v[9 * k], many40[k].v0, 12); std::memcpy(&v[9 * k + 3], many40[k].v1, 12); std::memcpy(&v[9 * k + 6], many40[k].v2, 12); }
+        CHECK(ptmi_update_mesh_vertices(c, v.data(), 39) == PTMI_EINVAL);
+        hipstub_poke("mesh_refit_check_kernel", 1, 0, (33u << 2) | 2u);
+        CHECK(ptmi_update_mesh_vertices(c, v.data(), 40) == PTMI_EINVAL && std::strstr(ptmi_last_error(c), "triangle 33"));
+        hipstub_clear_pokes();
+        injected += walk_failures(c, n, [&] { return ptmi_update_mesh_vertices(c, v.data(), 40); }, nothing, true);
+        std::memcpy(d_t, v.data(), v.size() * sizeof(float));
+        injected += walk_failures(c, n, [&] { return ptmi_update_mesh_vertices_device(c, static_cast<const float *>(d_t), 40); }, nothing, true);
+        CHECK(read_layout(c, n) == forty);
+        CHECK(hipFree(d_t) == hipSuccess);
     }
     CHECK(injected >= 20);
     std::printf("%s scene: %d injected failures\n", mesh ? "mesh" : "bvh", injected);

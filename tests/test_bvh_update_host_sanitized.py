@@ -1,9 +1,10 @@
-"""The host side of ptmi_update_spheres / ptmi_set_bvh_spheres under AddressSanitizer + UndefinedBehaviorSanitizer, without a GPU: a
+"""The host side of the scene's calls (csrc/ptmi_scene.cpp: ptmi_update_spheres, ptmi_set_bvh_spheres, ptmi_set_scene_bvh, ptmi_set_scene_mesh,
+ptmi_update_mesh_vertices, ptmi_set_mesh_triangles) under AddressSanitizer + UndefinedBehaviorSanitizer, without a GPU: a
 stand-alone program (tests/cxx/bvh_update_hostsan.cpp, its own main) linked against the library with instrumented host code and against
 the HIP stand-in (tests/cxx/hip_stub.cpp), and run directly in the environment as it is -- nothing is preloaded, nothing is loaded into Python.  The sanitizer's runtime is linked
 STATICALLY into the program (the library and the stand-in are built without one and find it there), so no order of libraries matters.  The program sets a
 BVH and a mesh scene, updates from host and stand-in device memory, sets spheres of another count, provokes every refusal and lets every
-runtime call of the new calls fail in turn, checking after each failure that the layout read back is the one before the call."""
+runtime call of these calls fail in turn, checking after each failure that the layouts read back are the ones before the call."""
 import os
 import subprocess
 import sys
