@@ -167,10 +167,21 @@ __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, f
     if (stashed) pass();
 }
 
+// How check_hit takes the square roots of a trace's sphere candidates (its FOLD parameter; measured per kernel family,
+// profiles/sphere_pass_ab.txt and experiments/sphere_pass/):
+//   kStash        dense passes, a candidate lane stashing (tca, x, index) in a masked block -- s_and_saveexec, three v_mov, s_or exec.  The
+//                 default: the Streams chain, the tree walk, the stream form's per-pixel kernels, the point queries;
+//   kStashSelect  dense passes, the stash as three selects (and the index's move).  render Inline: there the selects are the faster
+//                 stash (C2 2.63-2.65 ms against 2.64-2.66), in the tree walk they give the passes' gain away;
+//   kPerSphere    no stash: square root, t and the fold update at every sphere that has a candidate lane, for the whole wave, as every
+//                 kernel did before.  The stream form's split kernels (GLASS): their compacted waves hold a candidate in so many
+//                 lanes that nearly every such sphere meets a taken stash, and the stash only adds its moves (+0.4 % measured).
+enum class SphereFold { kStash, kStashSelect, kPerSphere };
+
 // check_hit is the same fold shaped for the SIMD:
 //   * the cheap part of every test (16 f32 operations for a sphere) runs for all lanes; the square
 //     root / division and the fold update run only when some lane of the wave can still be hit
-//     (wave-uniform branch on __any) -- the common case to skip once rays are incoherent;
+//     (wave-uniform branch on a ballot) -- the common case to skip once rays are incoherent;
 //   * best_key starts as NaN so that the first evaluated element always replaces the accumulator
 //     (`NaN <= key` is false), which is expMinWith seeding the fold with its head;
 //   * a skipped element is a Nothing (key FLT_MAX).  In the literal fold a Nothing replaces the
@@ -183,22 +194,64 @@ __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, f
 //     that holds its LDS address, four spheres per trip, the offsets as immediates.  The address of a wave-uniform LDS read is a
 //     scalar, but ds_read wants it in a VGPR: read as S[i] every ds_read_b128 had a `v_mov_b32 vN, sK` in front of it -- one
 //     VALU issue slot in 22 of the sphere test, 56 M of them per C2 launch (round 6, tools/isa_other.py: C2 2.93 -> 2.86 ms).
-template <bool STAGED = false, typename ScenePtr>
+//   * the sphere candidates' square roots run in DENSE PASSES (FOLD != kPerSphere), as fold_planes takes the planes' divisions.  On
+//     C2 a sphere with a candidate has it in 6 of the wave's 55 active lanes, 2.67 such spheres a trace: the whole wave paid for the
+//     correctly rounded root each time.  Now a candidate lane only STASHES (tca, x, i); which lanes hold a stash is a wave mask, so
+//     the bookkeeping is scalar.  A pass takes the square root, t, Just and key of every stashed lane's OWN sphere and folds it; it
+//     runs when a sphere comes up for a lane whose stash is taken, before that lane overwrites it, and once behind the last sphere
+//     (before the planes): never more passes than spheres with a candidate, which is what ran the square root before (C2: 1.42 a trace).
+//       - the same fold: a lane's stash is always its earliest candidate not yet folded, so the lane folds exactly its own candidates
+//         in ascending index with the same `<=` -- ties keep the earlier sphere -- and before any plane.
+//       - lanes without a stash sit OUT of a pass.  When the square root ran per sphere such a lane went through the update as a
+//         Nothing (key FLT_MAX), which replaces an accumulator that is still NaN (or +inf) and no other: all it could do was turn an
+//         unfilled accumulator into a Nothing.  Sitting out leaves best_just false and best_key NaN there instead.  Every later
+//         element replaces a NaN accumulator (`NaN <= key` is false); it replaced that Nothing too unless its own key is not <
+//         FLT_MAX -- another Nothing, which changes nothing a caller reads, or a Just that the final test below sends to the literal
+//         fold either way.  And no caller reads t or idx unless just.
+//       - sqrt_rn's whole-wave vote (__any(tiny)) sees the pass's lanes only, and in them only candidates' x: a wave takes the
+//         compiler's scaled sequence for fewer x than before, never for fewer than need it, and both sequences are the IEEE root.
+template <bool STAGED = false, SphereFold FOLD = SphereFold::kStash, typename ScenePtr>
 __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3 d, unsigned int *diag = nullptr)
 {
     float best_key = __builtin_nanf("");
     int best_idx = 0;
     bool best_just = false;
 
+    float stash_tca = 0.0f, stash_x = 0.0f;
+    int stash_idx = 0;
+    unsigned long long stashed = 0ull;                       // the lanes that hold a stash
+    auto pass = [&]() {
+        diag::sphere_pass(diag);
+        if (__builtin_amdgcn_inverse_ballot_w64(stashed)) {  // (the mask becomes the exec mask: no lane computes its own bit)
+            const float t = stash_tca - sqrt_rn(stash_x);    // min t0 t1 == t0 (thc >= 0 or NaN)
+            const bool just = !(t < 0.0f);                   // (a lane with a stash is a candidate)
+            const float key = just ? t : kInfinite;          // maybe infinite fst
+            // (as a masked block -- s_and_saveexec, two v_mov, s_or exec -- not as three selects: the selects cost C2 + 1.6 %, round 6)
+            if (!(best_key <= key)) { best_key = key; best_idx = stash_idx; best_just = just; }
+        }
+        stashed = 0ull;
+    };
     auto sphere = [&](const float4 g, int i) {
         PTMI_SPHERE_TEST(g, o, d);                           // tca, x, cand
         diag::sphere_test(diag, cand);
-        if (__any(cand)) {
-            const float t = tca - sqrt_rn(x);                // min t0 t1 == t0 (thc >= 0 or NaN)
-            const bool just = cand && !(t < 0.0f);
-            const float key = just ? t : kInfinite;          // maybe infinite fst
-            // (as a masked block -- s_and_saveexec, two v_mov, s_or exec -- not as three selects: the selects cost C2 + 1.6 %, round 6)
-            if (!(best_key <= key)) { best_key = key; best_idx = i; best_just = just; }
+        const unsigned long long cands = __ballot(cand);
+        if constexpr (FOLD == SphereFold::kPerSphere) {
+            if (cands) {
+                const float t = tca - sqrt_rn(x);            // min t0 t1 == t0 (thc >= 0 or NaN)
+                const bool just = cand && !(t < 0.0f);
+                const float key = just ? t : kInfinite;      // maybe infinite fst
+                if (!(best_key <= key)) { best_key = key; best_idx = i; best_just = just; }
+            }
+        } else if (cands) {
+            if (cands & stashed) pass();
+            if constexpr (FOLD == SphereFold::kStashSelect) {
+                stash_tca = cand ? tca : stash_tca;
+                stash_x = cand ? x : stash_x;
+                stash_idx = cand ? i : stash_idx;
+            } else {
+                if (cand) { stash_tca = tca; stash_x = x; stash_idx = i; asm volatile(""); }    // (the empty statement keeps the block from becoming selects)
+            }
+            stashed |= cands;
         }
     };
 
@@ -240,6 +293,7 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
         }
         if (i < ns) sphere(ga, i);
     }
+    if (FOLD != SphereFold::kPerSphere && stashed) pass();
     fold_planes([&](int k) -> float4 {
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (STAGED) return P[k]; else

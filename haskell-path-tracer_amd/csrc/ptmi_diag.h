@@ -4,7 +4,7 @@
 // non-static empty method -- a `this` that is never used -- was enough to move a few register assignments).  The macros, each set by the tool
 // that reads the counters back through ptmi_debug_counters (RenderArgs.work_counter):
 //   -DPTMI_PHASE_STATS   render_inline_kernel: lane participation and wave cycles per round       tools/phase_stats.py
-//   -DPTMI_SPHERE_STATS  check_hit: sphere tests that take the square-root path                   tools/phase_stats.py
+//   -DPTMI_SPHERE_STATS  check_hit: sphere tests with a candidate, dense sphere and plane passes      tools/phase_stats.py
 //   -DPTMI_TREE_STATS    render_streams_tree_kernel: lane participation, the wave's tail         tools/tree_stats.py
 //   -DPTMI_TREE_STATS_MAP   ... the red plane becomes the per-pixel cost map                     tools/tree_cost_map.py
 //   -DPTMI_TAIL_STATS    streams_pixels_kernel: when waves end, lanes with an item per trip      tools/tail_stats.py
@@ -40,7 +40,8 @@ PTMI_PROBE unsigned int wave_max(unsigned int v)
 
 // ---- check_hit: [16] sphere tests (per wave), [17] ... that took the square-root path, [18] candidate lanes, [19] active lanes,
 // [20] plane tests (per wave: the cheap part, every plane), [21] dense passes run (per wave: the division, each lane on its own lowest
-// pending plane -- fold_planes, ptmi_device.h)
+// pending plane -- fold_planes, ptmi_device.h), [22] dense sphere passes run (per wave: the square root, each lane on its own stashed
+// sphere -- check_hit; [17] then counts the tests that stash, and [22] / [17] is what the stash saves)
 #ifdef PTMI_SPHERE_STATS
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *work_counter) { return work_counter; }
 PTMI_PROBE void sphere_test(unsigned int *wc, bool cand)
@@ -61,11 +62,16 @@ PTMI_PROBE void plane_pass(unsigned int *wc)
 {
     if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 21, 1u);
 }
+PTMI_PROBE void sphere_pass(unsigned int *wc)
+{
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 22, 1u);
+}
 #else
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *) { return nullptr; }
 PTMI_PROBE static void sphere_test(unsigned int *, bool) {}
 PTMI_PROBE static void plane_test(unsigned int *) {}
 PTMI_PROBE static void plane_pass(unsigned int *) {}
+PTMI_PROBE static void sphere_pass(unsigned int *) {}
 #endif
 
 // ---- render Inline: [1] lane-trips, [2..4] lane participations in the shade round(s) and the trace round, [5] trips of the wave's

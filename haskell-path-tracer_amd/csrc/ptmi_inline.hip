@@ -7,6 +7,8 @@
 //     per-pixel order of RNG draws and of floating-point additions is exactly that of n_spp successive `render` calls;
 //   * the primitive list is staged into LDS once per workgroup and read as wave-wide broadcasts (every lane walks the same
 //     primitive at the same time);
+//   * a trace's sphere candidates keep (tca, x, index) in their lanes and take their square roots in dense passes, 1.4 a trace on C2
+//     where the whole wave ran the root 2.7 times (check_hit, ptmi_device.h: SphereFold::kStashSelect, the stash as selects);
 //   * a shade whose outcome the next prepareRay is certain to freeze only adds its emittance and draws (surely_frozen_after);
 //   * each LARGE block -- "start the pixel's next sample" -- is expanded once per trip: the sites that end a sample only set a
 //     per-lane flag, and one block at the top of the next trip acts on it (three inlined copies cost 3 %);
@@ -32,7 +34,7 @@ namespace {
 template <bool LDS_SCENE, int TILE_W = 0>
 __global__ void __launch_bounds__(kRenderBlock, PTMI_INLINE_WAVES) render_inline_kernel(const RenderArgs a)
 {
-#define PTMI_HIT(STAGED, ...) check_hit<STAGED>(__VA_ARGS__)
+#define PTMI_HIT(STAGED, ...) check_hit<STAGED, SphereFold::kStashSelect>(__VA_ARGS__)
 #define PTMI_HIT_RECORD hit_record
 #define PTMI_NORMAL_AT normal_at
 #include "ptmi_inline_body.inc"

@@ -109,7 +109,11 @@ def role_of(b, inner):
     if has("v_min_f32") and has("v_cmp_ngt_f32") and has("v_cmp_gt_u32") and b["valu"] <= 26:
         return "sphere_test"
     if has("v_sqrt_f32"):
-        return "sphere_candidate"
+        return "sphere_candidate"                  # a dense pass of the sphere fold: every stashed lane's square root (one copy per sphere site, one behind the walk)
+    if inner and b["valu"] == 3 and has("s_and_saveexec_b64") and all(o.startswith("v_mov_b32") for o in ops if o.startswith("v_")):
+        return "sphere_stash"                      # a candidate lane keeps (tca, x, index): the masked block behind the sphere test
+    if inner and b["valu"] == 4 and sum(o.startswith("v_cndmask_b32") for o in ops) == 3 and sum(o.startswith("v_mov_b32") for o in ops) == 1:
+        return "sphere_stash"                      # ... the same as three selects and the index's move (render Inline)
     if inner and has("v_cndmask_b32") and has("v_cmp_nle_f32") and b["valu"] <= 8 and not has("v_div_scale_f32"):
         return "sphere_candidate"                  # the fold update behind the square root
     if has("v_div_scale_f32") and (inner or has("v_cmp_nle_f32")):
@@ -168,7 +172,7 @@ def main():
                     other_ops[key] = other_ops.get(key, 0) + 1
         table.append({"label": label, "code": code, "valu": sum(counts.values()), "counts": counts, "other_ops": other_ops, "inner": len(loops) > 1})
     roles = {}
-    order = ["sphere_test", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
+    order = ["sphere_test", "sphere_stash", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
     for b in table:
         r = role_of(b, b["inner"]) or "rest_of_loop"
         roles.setdefault(r, []).append(b)
@@ -180,11 +184,13 @@ def main():
     fast_form = any(role_of(b, b["inner"]) == "sincos3_fast" for b in table)
     slow_arg = next((a for a in sys.argv[1:] if a.startswith("--slow-rounds=")), None)
     slow_rounds = (float(slow_arg.split("=")[1]) if slow_arg else 0.27 * e.get("shade", 0.0)) if fast_form else e.get("shade", 0.0)
-    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_candidate": e.get("sphere_sqrt_path"), "plane_test": e.get("plane_passes", e.get("plane_division_path")),
+    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_stash": e.get("sphere_sqrt_path"),
+                  "sphere_candidate": e.get("sphere_passes", e.get("sphere_sqrt_path")), "plane_test": e.get("plane_passes", e.get("plane_division_path")),
                   "sincos3_fast": e["shade"] - slow_rounds if e else None, "sincos_reduce": 3 * slow_rounds if e else None,
                   "sincos_polynomial": 3 * slow_rounds if e else None, "hit_normal": None,
                   "rest_of_loop": e.get("trips"), "sqrt_slow": 0, "division_fallback": 0}
-    what = {"sphere_test": "distanceTo @Sphere, the part every lane runs (16 f32 operations, the candidate test)", "sphere_candidate": "... its square root, t and the fold update, when a lane of the wave can be hit",
+    what = {"sphere_test": "distanceTo @Sphere, the part every lane runs (16 f32 operations, the candidate test)", "sphere_stash": "... a test with a candidate lane: the lane keeps (tca, x, index), three moves under the candidates' mask, or three selects and a move",
+            "sphere_candidate": "... a dense pass: square root, t and the fold update of every lane that holds a stash (before the plane fold: once per test with a candidate)",
             "plane_test": "distanceTo @Plane: a dense pass of the plane fold (each lane on its own stashed plane), IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade (with the fast form: per shade round that leaves it)",
             "sincos3_fast": "sin/cos of a shade's three half angles, quadrant by comparison: cvt, hpi - |x|, selects, the two f64 polynomials (the vote's 6 instructions sit with the draws, in rest_of_loop)",
             "sincos_polynomial": "sin/cos: the two f64 polynomials, sign and swap by bit operations", "hit_normal": "hit: the sphere normal's three divisions by one length",
@@ -204,8 +210,10 @@ def main():
                 ops[k] = ops.get(k, 0) + v
         if r == "sphere_test":
             copies = len(bs)
-        elif r == "sphere_candidate":
-            copies = max(1, len(roles.get("sphere_test", [])))
+        elif r == "sphere_stash":
+            copies = len(bs)
+        elif r == "sphere_candidate":                            # (with dense passes: one more copy behind the walk)
+            copies = max(1, len(roles.get("sphere_test", [])) + (1 if roles.get("sphere_stash") else 0))
         elif r == "plane_test":
             copies = max(1, sum(1 for b in bs if any(i.startswith("v_div_fixup") for i in b["code"])))
         elif r in ("sincos_reduce", "sincos_polynomial"):
