@@ -505,9 +505,16 @@ class Context:
         assert tuple(color.shape) == (3, self.local_rows, self.width), color.shape
         assert tuple(state.shape) == (4, self.local_rows, self.width), state.shape
         assert color.element_size() == 4 and state.element_size() == 4
-        ptrs = [color[i].data_ptr() for i in range(3)] + [state[i].data_ptr() for i in range(4)]
-        self._check(self._lib.ptmi_bind_planes(self._h, *[_vp(p) for p in ptrs]))
-        self._keep = [color, state]
+        self.bind_planes([color[i].data_ptr() for i in range(3)] + [state[i].data_ptr() for i in range(4)], keep=[color, state])
+
+    def bind_planes(self, ptrs, keep=None):
+        """ptmi_bind_planes with seven raw device addresses (ints; r g b sa sb sc sctr), each of local_rows x width 4-byte elements, 4-byte
+        aligned, anywhere relative to each other.  keep: whatever owns that memory, held alive while the binding stands."""
+        ptrs = list(ptrs)
+        if len(ptrs) != 7:
+            raise ValueError("seven plane addresses, not %d" % len(ptrs))
+        self._check(self._lib.ptmi_bind_planes(self._h, *[_vp(p) if p else None for p in ptrs]))
+        self._keep = [keep]
 
     def unbind(self):
         self._check(self._lib.ptmi_bind_planes(self._h, *([None] * 7)))

@@ -397,7 +397,12 @@ int ptmi_local_rows(const ptmi_ctx *ctx);                    /* rows held, or a 
 int ptmi_global_row(const ptmi_ctx *ctx, int local_row);     /* image row of a held row       */
 
 /* Use caller-owned DEVICE planes (e.g. torch tensors) of ptmi_local_rows() x width elements
- * instead of the context's own; pass all NULL to return to the owned planes. */
+ * instead of the context's own; pass all NULL to return to the owned planes.  A plane needs 4-byte alignment only (16-byte aligned
+ * planes let ptmi_present move four pixels per lane), and the seven may lie anywhere relative to each other: in any order, at any
+ * distance, in one allocation or seven.  Nothing is written outside the ptmi_local_rows() x width elements of each.  Some NULL and some
+ * not is PTMI_EINVAL and leaves the binding as it was; before ptmi_resize the call is PTMI_ESTATE.  ptmi_resize DROPS a binding:
+ * afterwards the context renders into fresh owned planes, zeroed, and the caller's planes are not written again until they are bound
+ * again.  Unbinding leaves the owned planes as they were when the caller's were bound: nothing is copied either way. */
 int ptmi_bind_planes(ptmi_ctx *ctx, float *r, float *g, float *b,
                      uint32_t *sa, uint32_t *sb, uint32_t *sc, uint32_t *sctr);
 /* The device addresses of the seven planes the context currently renders into (its own or the bound ones), for
