@@ -688,6 +688,7 @@ int launch_render(ptmi_ctx *c, const Planes &planes, const ptmi_camera *camera, 
     RenderArgs a{};
     a.cam = make_uniforms(*camera, width, height);
     a.scene.packed = c->scene.packed.as<float4>(); a.scene.n_spheres = (int)c->scene.rows.ns; a.scene.n_planes = (int)c->scene.rows.np;
+    a.scene.share_xy = c->scene.share_xy;
     a.planes = planes;
     a.screen_x = sx; a.screen_y = sy;
     a.width = width; a.height = height; a.rows_local = rows_local;
@@ -1721,6 +1722,7 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     PTMI_HIP(c, hipMemcpyAsync(d_rays, rays, nb * 6 * 4, hipMemcpyHostToDevice, c->stream));
     SceneView scene;
     scene.packed = c->scene.packed.as<float4>(); scene.n_spheres = (int)c->scene.rows.ns; scene.n_planes = (int)c->scene.rows.np;
+    scene.share_xy = c->scene.share_xy;
     if (c->scene.kind == SceneKind::Mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(scene, c->scene.mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
     else PTMI_HIP(c, launch_eval_check_hit(scene, c->scene.kind == SceneKind::Bvh ? &c->scene.bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(t_out, d_t, nb * 4, hipMemcpyDeviceToHost, c->stream));

@@ -80,6 +80,7 @@ struct SceneState {
     SceneKind kind = SceneKind::Linear;
     DeviceBlock packed, packed_shadow;                     // PackedRows; the second block is the sphere refit's, beside spheres.shadow
     PackedRows rows;
+    uint64_t share_xy = 0;                                 // a linear scene's spheres that repeat their predecessor's (cx, cy) bits (ptmi_share.h); else 0
     Hierarchy<SphereLayout> spheres;                       // a BVH or mesh scene
     Hierarchy<MeshLayout> triangles;                       // a mesh scene
     bool glass_spheres = false, glass_planes = false, glass_triangles = false;

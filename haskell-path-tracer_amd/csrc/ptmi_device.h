@@ -178,6 +178,17 @@ __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, f
 //                 lanes that nearly every such sphere meets a taken stash, and the stash only adds its moves (+0.4 % measured).
 enum class SphereFold { kStash, kStashSelect, kPerSphere };
 
+// Whether check_hit's walk carries the x-y terms of the sphere test from one sphere to the next (its SHARE parameter; chosen per kernel
+// family like FOLD, profiles/shared_xy_ab.txt and experiments/shared_xy/):
+//   kNone  every sphere runs PTMI_SPHERE_TEST whole.  The default;
+//   kXY    a sphere whose bit is set in `share` (SceneView.share_xy: its cx and cy have its predecessor's bits, ptmi_share.h) keeps the
+//          predecessor's sxy = lx dx + ly dy and qxy = lx lx + ly ly and forms tca = sxy + lz dz, d2 = (qxy + lz lz) - tca tca: 10 VALU
+//          instructions for 18.  render Inline on linear scenes (S16: 6 of 14 spheres) and the point queries, for a scene whose mask is not 0.
+//          In a scene without runs the walk would pay a scalar bit test and an untaken branch a sphere for nothing (C0's scene +0.6 %), and a
+//          second, untested walk behind a branch on mask == 0 costs render Inline a spill more than its budget allows (experiments/shared_xy/):
+//          the LAUNCHERS send a mask of 0 to a kNone kernel (render_inline_kernel_plain, ptmi_inline.hip; ptmi_small.hip).
+enum class SphereShare { kNone, kXY };
+
 // check_hit is the same fold shaped for the SIMD:
 //   * the cheap part of every test (16 f32 operations for a sphere) runs for all lanes; the square
 //     root / division and the fold update run only when some lane of the wave can still be hit
@@ -210,8 +221,15 @@ enum class SphereFold { kStash, kStashSelect, kPerSphere };
 //         fold either way.  And no caller reads t or idx unless just.
 //       - sqrt_rn's whole-wave vote (__any(tiny)) sees the pass's lanes only, and in them only candidates' x: a wave takes the
 //         compiler's scaled sequence for fewer x than before, never for fewer than need it, and both sequences are the IEEE root.
-template <bool STAGED = false, SphereFold FOLD = SphereFold::kStash, typename ScenePtr>
-__device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3 d, unsigned int *diag = nullptr)
+//   * SHARE = kXY: dot is (a.x b.x + a.y b.y) + a.z b.z (ptmi_core.h), so lx, ly, sxy = lx dx + ly dy and qxy = lx lx + ly ly are whole
+//     subexpressions of the test's literal arithmetic, and functions of (cx, cy) and the ray alone.  A sphere with its predecessor's cx
+//     and cy BITS would compute the same four values from the same operands: it takes them as they stand (a wave-uniform branch on the
+//     scene's mask, shifted along with the walk) and makes the rest of the test -- lz, tca, d2, x, cand -- by the macro's operations in
+//     the macro's order.  Shared or not, the same operations meet the same operands: the hits stay bit for bit PTMI_SPHERE_TEST's, which
+//     the hierarchies' walks (and kNone) keep running whole, so a BVH scene's hits stay the linear fold's.  Nothing is reordered (ties
+//     keep the earlier index), and the stash, the passes, the planes and the final test below see tca, x and cand as before.
+template <bool STAGED = false, SphereFold FOLD = SphereFold::kStash, SphereShare SHARE = SphereShare::kNone, typename ScenePtr>
+__device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3 d, unsigned int *diag = nullptr, unsigned long long share = 0ull)
 {
     float best_key = __builtin_nanf("");
     int best_idx = 0;
@@ -231,8 +249,10 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
         }
         stashed = 0ull;
     };
-    auto sphere = [&](const float4 g, int i) {
-        PTMI_SPHERE_TEST(g, o, d);                           // tca, x, cand
+    // (kXY) lx dx + ly dy and lx lx + ly ly of the last sphere that computed them.  Not initialised: bit 0 of the mask is never set, so the
+    // first sphere writes them before any reads them, and two moves a trace are 0.5 % of a small scene's instructions
+    float sxy, qxy;
+    auto fold_sphere = [&](int i, float tca, float x, bool cand) {
         diag::sphere_test(diag, cand);
         const unsigned long long cands = __ballot(cand);
         if constexpr (FOLD == SphereFold::kPerSphere) {
@@ -254,6 +274,27 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
             stashed |= cands;
         }
     };
+    // `bit`: which bit of `share` is this sphere's (the walks below shift the mask by a trip's spheres, so it is an immediate)
+    auto sphere = [&](const float4 g, int i, int bit = 0) {
+        if constexpr (SHARE == SphereShare::kXY) {
+            const float lz = g.z - o.z;
+            if (!((unsigned int)share & (1u << bit))) {      // wave-uniform: the mask is the scene's
+                const float lx = g.x - o.x, ly = g.y - o.y;
+                sxy = lx * d.x + ly * d.y;
+                qxy = lx * lx + ly * ly;
+            } else diag::sphere_shared(diag);
+            // PTMI_SPHERE_TEST from here on, operation for operation
+            const float tca = sxy + lz * d.z;
+            const float d2 = (qxy + lz * lz) - (tca * tca);
+            const float x = g.w - d2;
+            const bool cand = !(tca < 0.0f) && !(x < 0.0f);
+            fold_sphere(i, tca, x, cand);
+        } else {
+            (void)bit;
+            PTMI_SPHERE_TEST(g, o, d);                       // tca, x, cand
+            fold_sphere(i, tca, x, cand);
+        }
+    };
 
     float4 ga, gb;
     int i = 0;
@@ -266,19 +307,21 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
         P = (Staged)(uintptr_t)lds_at;
         ga = P[0];
         for (; i + 3 < ns; i += 4) {
-            gb = P[1]; sphere(ga, i);
-            ga = P[2]; sphere(gb, i + 1);
-            gb = P[3]; sphere(ga, i + 2);
-            ga = P[4]; sphere(gb, i + 3);                         // S has readable elements past the geometry
+            gb = P[1]; sphere(ga, i, 0);
+            ga = P[2]; sphere(gb, i + 1, 1);
+            gb = P[3]; sphere(ga, i + 2, 2);
+            ga = P[4]; sphere(gb, i + 3, 3);                      // S has readable elements past the geometry
             P += 4;
+            share >>= 4;                                          // (nothing is left of it from sphere 64 on)
         }
         for (; i + 1 < ns; i += 2) {
-            gb = P[1]; sphere(ga, i);
-            ga = P[2]; sphere(gb, i + 1);
+            gb = P[1]; sphere(ga, i, 0);
+            ga = P[2]; sphere(gb, i + 1, 1);
             P += 2;
+            share >>= 2;
         }
         if (i < ns) {
-            sphere(ga, i);
+            sphere(ga, i, 0);
             P += 1;
         }
     } else
@@ -287,11 +330,12 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
         ga = S[0];
         for (; i + 1 < ns; i += 2) {
             gb = S[i + 1];
-            sphere(ga, i);
+            sphere(ga, i, 0);
             ga = S[i + 2];                                       // S has readable elements past the geometry
-            sphere(gb, i + 1);
+            sphere(gb, i + 1, 1);
+            share >>= 2;
         }
-        if (i < ns) sphere(ga, i);
+        if (i < ns) sphere(ga, i, 0);
     }
     if (FOLD != SphereFold::kPerSphere && stashed) pass();
     fold_planes([&](int k) -> float4 {

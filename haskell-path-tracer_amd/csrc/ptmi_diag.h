@@ -41,7 +41,8 @@ PTMI_PROBE unsigned int wave_max(unsigned int v)
 // ---- check_hit: [16] sphere tests (per wave), [17] ... that took the square-root path, [18] candidate lanes, [19] active lanes,
 // [20] plane tests (per wave: the cheap part, every plane), [21] dense passes run (per wave: the division, each lane on its own lowest
 // pending plane -- fold_planes, ptmi_device.h), [22] dense sphere passes run (per wave: the square root, each lane on its own stashed
-// sphere -- check_hit; [17] then counts the tests that stash, and [22] / [17] is what the stash saves)
+// sphere -- check_hit; [17] then counts the tests that stash, and [22] / [17] is what the stash saves), [23] sphere tests (per wave, among
+// [16]'s) that took their predecessor's x-y terms (SphereShare::kXY)
 #ifdef PTMI_SPHERE_STATS
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *work_counter) { return work_counter; }
 PTMI_PROBE void sphere_test(unsigned int *wc, bool cand)
@@ -66,12 +67,17 @@ PTMI_PROBE void sphere_pass(unsigned int *wc)
 {
     if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 22, 1u);
 }
+PTMI_PROBE void sphere_shared(unsigned int *wc)
+{
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) atomicAdd(wc + 23, 1u);
+}
 #else
 PTMI_PROBE unsigned int *sphere_counters(unsigned int *) { return nullptr; }
 PTMI_PROBE static void sphere_test(unsigned int *, bool) {}
 PTMI_PROBE static void plane_test(unsigned int *) {}
 PTMI_PROBE static void plane_pass(unsigned int *) {}
 PTMI_PROBE static void sphere_pass(unsigned int *) {}
+PTMI_PROBE static void sphere_shared(unsigned int *) {}
 #endif
 
 // ---- render Inline: [1] lane-trips, [2..4] lane participations in the shade round(s) and the trace round, [5] trips of the wave's

@@ -28,12 +28,32 @@ namespace {
 // (scenes over 3 KB).  TILE_W: the wave's pixels are an 8 x 8 tile (8) or 64 consecutive pixels of a row (0).
 // The primary hit is evaluated once per pixel; loop [finish frozen shades + restart][shade][trace].
 // ---------------------------------------------------------------------------------------
+// (the diagnostic counters a trace passes to the hit search, or none: the primary hit's)
+__device__ __forceinline__ unsigned int *hit_diag(unsigned int *counters = nullptr) { return counters; }
+
 #ifndef PTMI_INLINE_WAVES
 #define PTMI_INLINE_WAVES 7      // 72 VGPRs (three registers spilled around the loop, not in it) and a 10-word LDS column: C2 3.10 -> 3.04 ms
 #endif
 template <bool LDS_SCENE, int TILE_W = 0>
 __global__ void __launch_bounds__(kRenderBlock, PTMI_INLINE_WAVES) render_inline_kernel(const RenderArgs a)
 {
+#define PTMI_HIT(STAGED, S, ns, np, o, d, ...) check_hit<STAGED, SphereFold::kStashSelect, SphereShare::kXY>(S, ns, np, o, d, hit_diag(__VA_ARGS__), a.scene.share_xy)
+#define PTMI_HIT_RECORD hit_record
+#define PTMI_NORMAL_AT normal_at
+#include "ptmi_inline_body.inc"
+#undef PTMI_HIT_RECORD
+#undef PTMI_NORMAL_AT
+#undef PTMI_HIT
+}
+
+// ... for a scene staged in LDS in which no sphere shares its predecessor's cx and cy (SceneView.share_xy == 0: mainScene): the same body, every
+// sphere running the whole test -- the kernel as it was before the sharing, instruction for instruction (tools/isa_diff.py), so that such
+// a scene pays nothing for the mask: no bit test, no branch.  The choice is the launcher's (launch_linear): the mask is known on the host.
+// (Inside one kernel a second, untested walk costs a spill more than the budget allows: experiments/shared_xy/.)
+template <int TILE_W = 0>
+__global__ void __launch_bounds__(kRenderBlock, PTMI_INLINE_WAVES) render_inline_kernel_plain(const RenderArgs a)
+{
+    constexpr bool LDS_SCENE = true;
 #define PTMI_HIT(STAGED, ...) check_hit<STAGED, SphereFold::kStashSelect>(__VA_ARGS__)
 #define PTMI_HIT_RECORD hit_record
 #define PTMI_NORMAL_AT normal_at
@@ -78,6 +98,9 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_BVH_WAVES) render_inline_me
 // the linear scenes' kernel: the scene staged in LDS or read through scalar loads, waves on tiles or rows as `mapping` says
 hipError_t launch_linear(const RenderArgs &a, Mapping mapping, bool lds_scene, hipStream_t stream)
 {
+    // (the scalar-load form is one kernel: a scene that big walks a mask of its first 64 spheres only, and pays its tests either way)
+    if (lds_scene && a.scene.share_xy == 0ull)
+        return launch_per_pixel(a, mapping, render_inline_kernel_plain<8>, render_inline_kernel_plain<0>, true, PTMI_INLINE_WAVES, 16, stream);
     if (lds_scene) return launch_per_pixel(a, mapping, render_inline_kernel<true, 8>, render_inline_kernel<true>, true, PTMI_INLINE_WAVES, 16, stream);
     return launch_per_pixel(a, mapping, render_inline_kernel<false, 8>, render_inline_kernel<false>, false, PTMI_INLINE_WAVES, 16, stream);
 }

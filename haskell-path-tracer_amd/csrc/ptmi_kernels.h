@@ -24,6 +24,7 @@ void context_size(const ptmi_ctx *ctx, int *width, int *height);
 struct SceneView {
     const float4 *packed;      // device memory
     int n_spheres, n_planes;
+    unsigned long long share_xy;   // bit i: sphere i has sphere i - 1's cx and cy bits (a linear scene's, ptmi_share.h; 0 otherwise)
     __host__ __device__ int geom_f4() const { return n_spheres + 2 * n_planes; }
     __host__ __device__ int total_f4() const { return geom_f4() + 2 * (n_spheres + n_planes); }
 };

@@ -13,6 +13,7 @@
 #include "ptmi_mesh.h"
 #include "ptmi_mesh_box.h"
 #include "ptmi_mesh_morton.h"
+#include "ptmi_share.h"
 
 using namespace ptmi;
 
@@ -26,6 +27,7 @@ struct Candidate {
     SceneKind kind = SceneKind::Linear;
     DeviceBlock packed, packed_shadow;
     PackedRows rows;
+    uint64_t share_xy = 0;                                 // of `packed` (shared_xy_mask, ptmi_share.h): a linear scene's; 0 for the hierarchies
     Hierarchy<SphereLayout> spheres;                       // block, plan (and, a refit's first, shadow) with their layouts, levels and box
     Hierarchy<MeshLayout> triangles;                       // block, shadow, plan
     bool refit_spheres = false, refit_triangles = false;   // the second blocks were written: they swap with the scene's (the boxes are new)
@@ -104,6 +106,8 @@ void commit(Candidate &k)
     // never move): whatever replaces either block frees the pair, and the next refit makes it afresh
     if (k.packed.p || k.spheres.block.p) { release(s.packed_shadow); release(s.spheres.shadow); }
     if (k.packed.p) { take(s.packed, k.packed); s.rows = k.rows; }
+    // the sharing mask is the packed block's: whatever replaces the block (or the whole scene) replaces the mask, so none outlives its spheres
+    if (k.packed.p || k.whole) s.share_xy = k.share_xy;
     if (k.spheres.block.p) take_tree(s.spheres, k.spheres);
     // (the mesh refit's second block comes with the block it copies)
     if (k.triangles.block.p) { take_tree(s.triangles, k.triangles); take(s.triangles.shadow, k.triangles.shadow); }
@@ -517,6 +521,7 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     k.glass_spheres = any_glass(spheres, n_spheres); k.glass_planes = any_glass(planes, n_planes); k.glass_triangles = 0;
     std::vector<float4> packed;
     pack_scene(k.rows, spheres, planes, nullptr, packed);
+    k.share_xy = shared_xy_mask(&packed[0].x, 4, n_spheres);  // of the rows the kernels read
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     // the new scene stands complete before the old one goes
     k.alloc(k.packed, k.rows.bytes());

@@ -124,7 +124,9 @@ __global__ void __launch_bounds__(kBlock) eval_sphere_kernel(const float *sph, c
 }
 
 // checkHit (Trace.hs:443-447) on the context's scene for host rays: the render kernels' hit search (check_hit over the packed scene,
-// check_hit_bvh over a BVH scene), one lane per ray.  A miss is reported as t = 0, idx = -1.
+// check_hit_bvh over a BVH scene), one lane per ray.  A miss is reported as t = 0, idx = -1.  SHARE: a linear scene with runs (its mask is not
+// 0) shares the x-y terms as render Inline does -- the plain walk's two spheres a trip; one without runs takes the walk that shares nothing,
+// as render Inline does (launch_eval_check_hit chooses eval_check_hit_shared_kernel or this one), so both walks stay reachable from the point queries.
 template <bool BVH>
 __global__ void __launch_bounds__(kRenderBlock) eval_check_hit_kernel(const SceneView scene, const BvhView bvh, const float *rays, int n,
                                                                       float *t_out, int32_t *idx_out, int32_t *just_out)
@@ -135,6 +137,20 @@ __global__ void __launch_bounds__(kRenderBlock) eval_check_hit_kernel(const Scen
     const V3 d = mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
     const HitSel h = BVH ? check_hit_bvh(bvh, scene.packed, scene.n_spheres, scene.n_planes, o, d)
                          : check_hit(scene.packed, scene.n_spheres, scene.n_planes, o, d);
+    just_out[i] = h.just ? 1 : 0;
+    t_out[i] = h.just ? h.t : 0.0f;
+    idx_out[i] = h.just ? h.idx : -1;
+}
+
+// ... over a linear scene with runs (SphereShare::kXY)
+__global__ void __launch_bounds__(kRenderBlock) eval_check_hit_shared_kernel(const SceneView scene, const float *rays, int n,
+                                                                             float *t_out, int32_t *idx_out, int32_t *just_out)
+{
+    const int i = blockIdx.x * kRenderBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
+    const V3 d = mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
+    const HitSel h = check_hit<false, SphereFold::kStash, SphereShare::kXY>(scene.packed, scene.n_spheres, scene.n_planes, o, d, nullptr, scene.share_xy);
     just_out[i] = h.just ? 1 : 0;
     t_out[i] = h.just ? h.t : 0.0f;
     idx_out[i] = h.just ? h.idx : -1;
@@ -286,6 +302,7 @@ hipError_t launch_eval_check_hit(SceneView scene, const BvhView *bvh, const floa
     if (n <= 0) return hipSuccess;
     const dim3 grid(blocks_for(n, kRenderBlock)), block(kRenderBlock);
     if (bvh) return launch(eval_check_hit_kernel<true>, grid, block, 0, stream, scene, *bvh, rays, n, t, idx, just);
+    if (scene.share_xy) return launch(eval_check_hit_shared_kernel, grid, block, 0, stream, scene, rays, n, t, idx, just);
     return launch(eval_check_hit_kernel<false>, grid, block, 0, stream, scene, BvhView{}, rays, n, t, idx, just);
 }
 

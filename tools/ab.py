@@ -6,7 +6,7 @@
 
 Workloads (1080p, 64 spp, ms per launch, best of N after warm-up): c2 (render Inline, scene S16), streams (per-pixel
 Streams, S16), s16_stream (stream form, S16), glass_tree (per-pixel tree walk, glass scene), glass_stream (stream form); c5_tree /
-c5_stream: one of 8 parts of the 4K / 512-spp glass image; suffixes _uniform (PTMI_OPT_STREAM_GRADED = 0), _gK (PTMI_OPT_GLASS_BATCH = K),
+c5_stream: one of 8 parts of the 4K / 512-spp glass image; c0 (render Inline, mainScene, 800 x 600); suffixes _uniform (PTMI_OPT_STREAM_GRADED = 0), _gK (PTMI_OPT_GLASS_BATCH = K),
 _bK (PTMI_OPT_STREAM_BATCH = K)."""
 import glob
 import json
@@ -46,6 +46,8 @@ for _tag, _shape in (("c4p", C4_PART), ("c4p256", C4_PART_256)):           # the
     for _k in (4, 8):
         WORKLOADS[_tag + "_stream_%dfenced" % _k] = ("s16", "streams", "stream", {"ORDERED_PASSES": _k, "PASS_HANDOFF": 0}, _shape)
         WORKLOADS[_tag + "_stream_%dfree" % _k] = ("s16", "streams", "stream", {"ORDERED_PASSES": _k, "PASS_HANDOFF": 1}, _shape)
+WORKLOADS["c0"] = ("main", "inline", "auto", {}, (800, 600, 64, 1))         # C0's scene and image (mainScene: no two spheres share cx and cy), 64 spp a launch
+WORKLOADS["c0_streams"] = ("main", "streams", "auto", {}, (800, 600, 64, 1))  # ... through the Streams chain
 WORKLOADS["c4_part"] = ("s16", "inline", "auto", {}, C4_PART)
 WORKLOADS["c4_part_streams"] = ("s16", "streams", "auto", {}, C4_PART)
 for _k in (1, 2, 4, 5, 6, 8, 12, 16):

@@ -108,6 +108,9 @@ def role_of(b, inner):
         return "sqrt_slow"                         # the compiler's denormal-scaled square root: only when a lane holds 0 < x < 2^-96
     if has("v_min_f32") and has("v_cmp_ngt_f32") and has("v_cmp_gt_u32") and b["valu"] <= 26:
         return "sphere_test"
+    valu_ops = [o for o in ops if o.startswith("v_")]
+    if inner and b["valu"] == 8 and sorted(o.rsplit("_", 1)[0] for o in valu_ops) == ["v_add_f32"] * 2 + ["v_mul_f32"] * 4 + ["v_sub_f32"] * 2:
+        return "sphere_xy"                         # the x-y terms of the sphere test, skipped by a sphere that shares its predecessor's (SphereShare::kXY)
     if has("v_sqrt_f32"):
         return "sphere_candidate"                  # a dense pass of the sphere fold: every stashed lane's square root (one copy per sphere site, one behind the walk)
     if inner and b["valu"] == 3 and has("s_and_saveexec_b64") and all(o.startswith("v_mov_b32") for o in ops if o.startswith("v_")):
@@ -172,7 +175,7 @@ def main():
                     other_ops[key] = other_ops.get(key, 0) + 1
         table.append({"label": label, "code": code, "valu": sum(counts.values()), "counts": counts, "other_ops": other_ops, "inner": len(loops) > 1})
     roles = {}
-    order = ["sphere_test", "sphere_stash", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
+    order = ["sphere_test", "sphere_xy", "sphere_stash", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
     for b in table:
         r = role_of(b, b["inner"]) or "rest_of_loop"
         roles.setdefault(r, []).append(b)
@@ -184,12 +187,14 @@ def main():
     fast_form = any(role_of(b, b["inner"]) == "sincos3_fast" for b in table)
     slow_arg = next((a for a in sys.argv[1:] if a.startswith("--slow-rounds=")), None)
     slow_rounds = (float(slow_arg.split("=")[1]) if slow_arg else 0.27 * e.get("shade", 0.0)) if fast_form else e.get("shade", 0.0)
-    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_stash": e.get("sphere_sqrt_path"),
+    role_execs = {"sphere_test": e.get("sphere_tests"), "sphere_xy": e["sphere_tests"] - e["sphere_shared"] if "sphere_tests" in e and "sphere_shared" in e else None,   # (unknown without the shared-test counter)
+                  "sphere_stash": e.get("sphere_sqrt_path"),
                   "sphere_candidate": e.get("sphere_passes", e.get("sphere_sqrt_path")), "plane_test": e.get("plane_passes", e.get("plane_division_path")),
                   "sincos3_fast": e["shade"] - slow_rounds if e else None, "sincos_reduce": 3 * slow_rounds if e else None,
                   "sincos_polynomial": 3 * slow_rounds if e else None, "hit_normal": None,
                   "rest_of_loop": e.get("trips"), "sqrt_slow": 0, "division_fallback": 0}
-    what = {"sphere_test": "distanceTo @Sphere, the part every lane runs (16 f32 operations, the candidate test)", "sphere_stash": "... a test with a candidate lane: the lane keeps (tca, x, index), three moves under the candidates' mask, or three selects and a move",
+    what = {"sphere_test": "distanceTo @Sphere, the part every lane runs at every sphere (lz, tca, d2, x, the candidate test)",
+            "sphere_xy": "... its x-y terms (lx, ly, lx dx + ly dy, lx lx + ly ly): every sphere but those that share their predecessor's cx and cy", "sphere_stash": "... a test with a candidate lane: the lane keeps (tca, x, index), three moves under the candidates' mask, or three selects and a move",
             "sphere_candidate": "... a dense pass: square root, t and the fold update of every lane that holds a stash (before the plane fold: once per test with a candidate)",
             "plane_test": "distanceTo @Plane: a dense pass of the plane fold (each lane on its own stashed plane), IEEE division and fold update", "sincos_reduce": "sin/cos: argument reduction (f64), three per shade (with the fast form: per shade round that leaves it)",
             "sincos3_fast": "sin/cos of a shade's three half angles, quadrant by comparison: cvt, hpi - |x|, selects, the two f64 polynomials (the vote's 6 instructions sit with the draws, in rest_of_loop)",
@@ -208,7 +213,7 @@ def main():
         for b in bs:
             for k, v in b["other_ops"].items():
                 ops[k] = ops.get(k, 0) + v
-        if r == "sphere_test":
+        if r in ("sphere_test", "sphere_xy"):
             copies = len(bs)
         elif r == "sphere_stash":
             copies = len(bs)
