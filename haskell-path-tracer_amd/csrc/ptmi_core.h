@@ -218,8 +218,8 @@ PTMI_HD void sincos(float y, float &sn, float &cs) { sincos_t<PTMI_SINCOS_FUSED 
 // Inside (kQuadT2n, kQuadT2p) two binary32 compares therefore give n, (double)n * hpi is exactly 0 or +-hpi, and the sign / negate / swap
 // of sincos_t -- (m + 1) & 2, m & 2, n & 1 with m = n -- are: flip the argument iff n = +1, negate the cosine polynomial iff n = -1, swap
 // iff n != 0.  No conversion to an integer and back, no f64 multiplication, no range skeleton.
-// The form does NOT cover |y| < 2^-12 (sn = y, cs = 1), anything at or beyond +-T2, inf or NaN: sincos3_wave_is_fast sends a wave that
-// holds one such angle in any active lane to sincos() three times.  tools/verify_sincos_quadrant.cpp (host) and
+// The form does NOT cover |y| < 2^-12 (sn = y, cs = 1; sincos_tiny_fixup below adds it), anything at or beyond +-T2, inf or NaN: a wave that
+// holds an angle of the latter kind in any active lane goes to sincos() three times (sincos3_wave_in_range).  tools/verify_sincos_quadrant.cpp (host) and
 // tools/verify_sincos_quadrant.hip (device, profiles/verify_sincos_quadrant.txt) compare it bitwise with sincos_t<false> for every binary32
 // in the range.
 constexpr uint32_t kQuadT1p = 0x3f490fdbu, kQuadT1n = 0xbf490fddu, kQuadT2p = 0x4016cbe4u, kQuadT2n = 0xc016cbe5u;
@@ -250,6 +250,29 @@ PTMI_HD void sincos_quadrant(float y, float &sn, float &cs)
     cs = turned ? S : Cp;
 }
 
+// ... and |y| < 2^-12 inside the fast form.  For top < 0x398 sincos_t returns (y, 1) whatever its polynomials gave -- that is its last line --
+// and such an angle lies in quadrant 0, inside (kQuadT2n, kQuadT2p): sincos_quadrant runs on it like on any other (finite operands, results
+// thrown away) and the same last line follows, zeros and denormals included.  S16's Glossy sphere with p = 1 draws three zero angles at every
+// hit and its other Glossy surfaces (hk = 0.05, 0.1) one angle below 2^-12 in a few hundred: 27 % of C2's shade rounds held such a lane and
+// went to sincos() three times.  The guards that stood before this keep their names and meaning (tools/verify_sincos_quadrant.cpp reports them).
+// true iff sincos_quadrant followed by sincos_tiny_fixup is valid for y: kQuadT2n < y < kQuadT2p as numbers; NaN and inf answer false
+PTMI_HD bool sincos_quadrant_tiny_covers(float y)
+{
+    const uint32_t b = f2u(y);
+    return (int32_t)b < (int32_t)kQuadT2p && b < kQuadT2n;
+}
+PTMI_HD bool sincos_is_tiny(float y) { return (f2u(y) & 0x7fffffffu) < kQuadTiny; }      // sincos_t's top < 0x398
+PTMI_HD void sincos_tiny_fixup(float y, float &sn, float &cs)
+{
+    if (sincos_is_tiny(y)) { sn = y; cs = 1.0f; }
+}
+// the per-angle form of the render kernels' fast path, for sincos_quadrant_tiny_covers(y) (tests/cxx/sincos_tiny_main.cpp)
+PTMI_HD void sincos_quadrant_tiny(float y, float &sn, float &cs)
+{
+    sincos_quadrant(y, sn, cs);
+    sincos_tiny_fixup(y, sn, cs);
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // One guard per wave for the three angles: every active lane's three angles inside the quadrant form's range.  On the bit patterns, so that
 // a NaN cannot hide behind a maximum: as SIGNED integers the positive floats are ordered like their values and every negative one is below
@@ -265,6 +288,19 @@ __device__ __forceinline__ bool sincos3_wave_is_fast(float a, float b, float c)
     const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b)), __builtin_fabsf(c));
     return __builtin_amdgcn_ballot_w64(!(smax < (int32_t)kQuadT2p && umax < kQuadT2n && amin >= u2f(kQuadTiny))) == 0;
 }
+
+// The same three compares as TWO votes: the answer is whether every active lane's three angles are inside (kQuadT2n, kQuadT2p) -- the range of
+// sincos_quadrant_tiny --, and `tiny` whether any of them holds an angle below 2^-12 in magnitude (meaningful when the answer is true: no NaN).
+__device__ __forceinline__ bool sincos3_wave_in_range(float a, float b, float c, bool &tiny)
+{
+    const int32_t ia = (int32_t)f2u(a), ib = (int32_t)f2u(b), ic = (int32_t)f2u(c);
+    const int32_t smax = ia > ib ? (ia > ic ? ia : ic) : (ib > ic ? ib : ic);
+    const uint32_t ua = f2u(a), ub = f2u(b), uc = f2u(c);
+    const uint32_t umax = ua > ub ? (ua > uc ? ua : uc) : (ub > uc ? ub : uc);
+    const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b)), __builtin_fabsf(c));
+    tiny = __builtin_amdgcn_ballot_w64(!(amin >= u2f(kQuadTiny))) != 0;
+    return __builtin_amdgcn_ballot_w64(!(smax < (int32_t)kQuadT2p && umax < kQuadT2n)) == 0;
+}
 #endif
 
 // anglesToQuaternion (src/Util.hs:55-67) from the three HALF angles (yaw*0.5 etc. already formed).  Every lane of the wave that shades is
@@ -272,7 +308,22 @@ __device__ __forceinline__ bool sincos3_wave_is_fast(float a, float b, float c)
 PTMI_HD Quat quaternion_from_half_angles(float half_roll, float half_pitch, float half_yaw)
 {
     float sr, cr, sp, cp, sy, cy;
-#if defined(__HIP_DEVICE_COMPILE__) && PTMI_SINCOS_FUSED != 0 && !defined(PTMI_SINCOS_PER_ANGLE)
+#if defined(__HIP_DEVICE_COMPILE__) && PTMI_SINCOS_FUSED != 0 && !defined(PTMI_SINCOS_PER_ANGLE) && !defined(PTMI_NO_SINCOS_TINY)
+    // three outcomes of one vote: an angle at or beyond +-T2, inf or NaN in any active lane -- three sincos(), below; otherwise the quadrant form
+    // for every lane, and behind a second wave-uniform branch its last line for the lanes whose angle is below 2^-12
+    bool tiny;
+    if (__builtin_expect(sincos3_wave_in_range(half_roll, half_pitch, half_yaw, tiny), 1)) {
+        sincos_quadrant(half_roll, sr, cr);
+        if (tiny) sincos_tiny_fixup(half_roll, sr, cr);
+        // keep the three f64 evaluations from being interleaved: their temporaries are the kernel's VGPR peak
+        __builtin_amdgcn_sched_barrier(0);
+        sincos_quadrant(half_pitch, sp, cp);
+        if (tiny) sincos_tiny_fixup(half_pitch, sp, cp);
+        __builtin_amdgcn_sched_barrier(0);
+        sincos_quadrant(half_yaw, sy, cy);
+        if (tiny) sincos_tiny_fixup(half_yaw, sy, cy);
+    } else
+#elif defined(__HIP_DEVICE_COMPILE__) && PTMI_SINCOS_FUSED != 0 && !defined(PTMI_SINCOS_PER_ANGLE)
     if (__builtin_expect(sincos3_wave_is_fast(half_roll, half_pitch, half_yaw), 1)) {
         sincos_quadrant(half_roll, sr, cr);
         // keep the three f64 evaluations from being interleaved: their temporaries are the kernel's VGPR peak

@@ -28,6 +28,25 @@ constexpr bool kStagedWalk = false;
 constexpr bool kStagedWalk = true;
 #endif
 
+// Whole-wave votes of the render loops as scalar work: __any(c) / __all(c) come out as v_cndmask 0, 1 and v_cmp_ne_u32 on top of c's own
+// compare -- two four-cycle issue slots for what s_cmp does on the mask that compare already left in an SGPR pair.
+__device__ __forceinline__ bool wave_any(bool c)
+{
+#ifdef PTMI_NO_SCALAR_VOTES
+    return __any(c);
+#else
+    return __builtin_amdgcn_ballot_w64(c) != 0ull;
+#endif
+}
+__device__ __forceinline__ bool wave_all(bool c)
+{
+#ifdef PTMI_NO_SCALAR_VOTES
+    return __all(c);
+#else
+    return __builtin_amdgcn_ballot_w64(!c) == 0ull;
+#endif
+}
+
 // Correctly rounded binary32 square root (== IEEE sqrtf, which is what the reference's `sqrt`
 // lowers to) without the compiler's always-on denormal scaling: v_sqrt_f32 is within 1 ulp, two
 // exact FMA residuals pick the neighbour.  The residual test needs x == 0 or x >= 2^-96; if ANY
@@ -35,7 +54,7 @@ constexpr bool kStagedWalk = true;
 __device__ __forceinline__ float sqrt_rn(float x)
 {
     const bool tiny = (f2u(x) - 1u) < (0x0f800000u - 1u);          // 0 < x < 2^-96
-    if (__builtin_expect(__any(tiny), 0)) return __builtin_sqrtf(x);
+    if (__builtin_expect(wave_any(tiny), 0)) return __builtin_sqrtf(x);
     const float s = __builtin_amdgcn_sqrtf(x);
     const float s_dn = u2f(f2u(s) - 1u), s_up = u2f(f2u(s) + 1u);
     const float e_dn = __builtin_fmaf(-s_dn, s, x);
@@ -60,7 +79,7 @@ __device__ __forceinline__ V3 div3_by_length(V3 v, float s)
 #else
     const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), __builtin_fabsf(v.z));
     const bool plain = s >= 0x1p-20f && s <= 0x1p20f && amin >= 0x1p-100f;
-    if (__builtin_expect(!__all(plain), 0)) return div_r(v, s);
+    if (__builtin_expect(!wave_all(plain), 0)) return div_r(v, s);
     const float r0 = __builtin_amdgcn_rcpf(s);
     const float r = __builtin_fmaf(__builtin_fmaf(-s, r0, 1.0f), r0, r0);
     auto quotient = [&](float a) {
@@ -109,10 +128,14 @@ __device__ __noinline__ HitSel check_hit_exact(ScenePtr S, int ns, int np, V3 o,
 // distanceTo @Sphere (Intersection.hs:39-48) up to the square root, for g = (cx, cy, cz, r*r): declares tca, x and cand.  t = tca -
 // sqrt_rn(x) (min t0 t1 == t0), Just iff cand && !(t < 0).  A macro, so that check_hit and check_hit_bvh (ptmi_bvh_device.h) make
 // the SAME operations -- a BVH scene's hits are bit for bit the linear fold's -- and check_hit's code stays what it was.
-#define PTMI_SPHERE_TEST(g, o, d)                                                                                                   \
+// PTMI_SPHERE_TERMS is the macro up to d2: check_hit's walk forms the candidates from tca and d2 as a wave mask and x = r2 - d2 only where a
+// lane is one (fold_sphere); the hierarchies' walks take every lane's square root at a leaf and keep the macro whole.
+#define PTMI_SPHERE_TERMS(g, o, d)                                                                                                  \
     const V3 l = mk(g.x, g.y, g.z) - o;                                                                                             \
     const float tca = dot(l, d);                                                                                                    \
-    const float d2 = dot(l, l) - (tca * tca);                                                                                       \
+    const float d2 = dot(l, l) - (tca * tca)
+#define PTMI_SPHERE_TEST(g, o, d)                                                                                                   \
+    PTMI_SPHERE_TERMS(g, o, d);                                                                                                     \
     const float x = g.w - d2;                            /* rad ** 2 - d2 (rad ** 2 squared at upload) */                           \
     /* Nothing iff tca < 0 || d2 > rad**2 || t < 0;  d2 > r2 <=> r2 - d2 < 0 (exact: gradual underflow) */                         \
     const bool cand = !(tca < 0.0f) && !(x < 0.0f)
@@ -189,6 +212,15 @@ enum class SphereFold { kStash, kStashSelect, kPerSphere };
 //          the LAUNCHERS send a mask of 0 to a kNone kernel (render_inline_kernel_plain, ptmi_inline.hip; ptmi_small.hip).
 enum class SphereShare { kNone, kXY };
 
+// A/B builds (tools/ab.py, profiles/four_cycle_ab.txt): -DPTMI_NO_SPHERE_TWO_COMPARES forms check_hit's candidates as it did (x for every
+// lane, one compare of min(tca, x)), -DPTMI_NO_SCALAR_VOTES leaves the whole-wave votes to __any / __all,
+// -DPTMI_NO_SINCOS_TINY sends a wave that holds an angle below 2^-12 to sincos() (ptmi_core.h).
+#ifdef PTMI_NO_SPHERE_TWO_COMPARES
+constexpr bool kSphereTwoCompares = false;
+#else
+constexpr bool kSphereTwoCompares = true;
+#endif
+
 // check_hit is the same fold shaped for the SIMD:
 //   * the cheap part of every test (16 f32 operations for a sphere) runs for all lanes; the square
 //     root / division and the fold update run only when some lane of the wave can still be hit
@@ -224,7 +256,7 @@ enum class SphereShare { kNone, kXY };
 //   * SHARE = kXY: dot is (a.x b.x + a.y b.y) + a.z b.z (ptmi_core.h), so lx, ly, sxy = lx dx + ly dy and qxy = lx lx + ly ly are whole
 //     subexpressions of the test's literal arithmetic, and functions of (cx, cy) and the ray alone.  A sphere with its predecessor's cx
 //     and cy BITS would compute the same four values from the same operands: it takes them as they stand (a wave-uniform branch on the
-//     scene's mask, shifted along with the walk) and makes the rest of the test -- lz, tca, d2, x, cand -- by the macro's operations in
+//     scene's mask, shifted along with the walk) and makes the rest of the test -- lz, tca, d2, then fold_sphere's x and candidates -- by the macro's operations in
 //     the macro's order.  Shared or not, the same operations meet the same operands: the hits stay bit for bit PTMI_SPHERE_TEST's, which
 //     the hierarchies' walks (and kNone) keep running whole, so a BVH scene's hits stay the linear fold's.  Nothing is reordered (ties
 //     keep the earlier index), and the stash, the passes, the planes and the final test below see tca, x and cand as before.
@@ -252,11 +284,26 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
     // (kXY) lx dx + ly dy and lx lx + ly ly of the last sphere that computed them.  Not initialised: bit 0 of the mask is never set, so the
     // first sphere writes them before any reads them, and two moves a trace are 0.5 % of a small scene's instructions
     float sxy, qxy;
-    auto fold_sphere = [&](int i, float tca, float x, bool cand) {
+    // (kTwoCompares) the candidates of a sphere as a WAVE MASK from two compares, tca < 0 and d2 > r2, joined by one scalar and: x = r2 - d2
+    // is then needed only where a lane is a candidate (a fifth of the tests on C2) and is formed there, by the same subtraction.  d2 > r2 is
+    // the predicate x < 0 (see PTMI_SPHERE_TEST; r2 = inf with d2 = inf and every NaN answer false to both), so tca, x and the candidates
+    // are the macro's bit for bit, and the stash's selects and `stashed` take the scalar mask as it stands.
+    auto fold_sphere = [&](int i, float tca, float d2, float r2) {
+        float x = 0.0f;
+        bool cand;
+        unsigned long long cands;
+        if constexpr (kSphereTwoCompares) {
+            cands = __builtin_amdgcn_ballot_w64(!(tca < 0.0f)) & __builtin_amdgcn_ballot_w64(!(d2 > r2));
+            cand = __builtin_amdgcn_inverse_ballot_w64(cands);
+        } else {
+            x = r2 - d2;
+            cand = !(tca < 0.0f) && !(x < 0.0f);
+            cands = __ballot(cand);
+        }
         diag::sphere_test(diag, cand);
-        const unsigned long long cands = __ballot(cand);
         if constexpr (FOLD == SphereFold::kPerSphere) {
             if (cands) {
+                if constexpr (kSphereTwoCompares) x = r2 - d2;
                 const float t = tca - sqrt_rn(x);            // min t0 t1 == t0 (thc >= 0 or NaN)
                 const bool just = cand && !(t < 0.0f);
                 const float key = just ? t : kInfinite;      // maybe infinite fst
@@ -264,6 +311,7 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
             }
         } else if (cands) {
             if (cands & stashed) pass();
+            if constexpr (kSphereTwoCompares) x = r2 - d2;
             if constexpr (FOLD == SphereFold::kStashSelect) {
                 stash_tca = cand ? tca : stash_tca;
                 stash_x = cand ? x : stash_x;
@@ -286,13 +334,11 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
             // PTMI_SPHERE_TEST from here on, operation for operation
             const float tca = sxy + lz * d.z;
             const float d2 = (qxy + lz * lz) - (tca * tca);
-            const float x = g.w - d2;
-            const bool cand = !(tca < 0.0f) && !(x < 0.0f);
-            fold_sphere(i, tca, x, cand);
+            fold_sphere(i, tca, d2, g.w);                    // x, cand
         } else {
             (void)bit;
-            PTMI_SPHERE_TEST(g, o, d);                       // tca, x, cand
-            fold_sphere(i, tca, x, cand);
+            PTMI_SPHERE_TERMS(g, o, d);                      // tca, d2
+            fold_sphere(i, tca, d2, g.w);                    // x, cand
         }
     };
 
@@ -344,7 +390,16 @@ __device__ __forceinline__ HitSel check_hit(ScenePtr S, int ns, int np, V3 o, V3
 #endif
         return S[ns + k];
     }, ns, np, o, d, best_key, best_idx, best_just, diag);
+    // (the vote on ONE compare, of the key a Just holds and 0 otherwise: the ballot of a two-term condition goes back through a VGPR)
+#ifdef PTMI_NO_SCALAR_VOTES
     if (__builtin_expect(__any(best_just && !(best_key < kInfinite)), 0))
+#else
+    float just_key = best_just ? best_key : 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(just_key));                       // (... and the compiler folds the select back into that condition)
+#endif
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(just_key < kInfinite)) != 0ull, 0))
+#endif
         return check_hit_exact(S, ns, np, o, d);
     HitSel best; best.t = best_key; best.idx = best_idx; best.just = best_just;
     return best;
@@ -419,14 +474,20 @@ __device__ __forceinline__ void next_about_axis(float4 mb, V3 axis, float hk, Sf
 
 // -DPTMI_SINCOS_STATS (diagnostic build, tools/sincos_stats.py): called before next_about_axis with a COPY of the seed, it makes the three
 // draws again and votes as quaternion_from_half_angles will: [30] shade rounds of a wave, [31] those that leave the three-angle fast form
-// (an angle below 2^-12 in magnitude, beyond +-T2, inf or NaN in any lane that shades).  Empty and static otherwise, like diag's probes.
+// (an angle beyond +-T2, inf or NaN in any lane that shades; with -DPTMI_NO_SINCOS_TINY also one below 2^-12 in magnitude), [29] those that
+// stay in it and run the fix-up for angles below 2^-12.  Empty and static otherwise, like diag's probes.
 #ifdef PTMI_SINCOS_STATS
 __device__ __forceinline__ void sincos3_probe(unsigned int *wc, float hk, Sfc32 seed)
 {
 #if defined(__HIP_DEVICE_COMPILE__)                                  // (the vote exists in the device pass only)
     const float x = gen_component(seed), y = gen_component(seed), z = gen_component(seed);
-    const bool fast = sincos3_wave_is_fast(hk * x, hk * y, hk * z);
-    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) { atomicAdd(wc + 30, 1u); if (!fast) atomicAdd(wc + 31, 1u); }
+#ifdef PTMI_NO_SINCOS_TINY
+    const bool fast = sincos3_wave_is_fast(hk * x, hk * y, hk * z), tiny = false;
+#else
+    bool tiny;
+    const bool fast = sincos3_wave_in_range(hk * x, hk * y, hk * z, tiny);
+#endif
+    if (wc && (threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(1))) { atomicAdd(wc + 30, 1u); if (!fast) atomicAdd(wc + 31, 1u); else if (tiny) atomicAdd(wc + 29, 1u); }
 #endif
 }
 #else

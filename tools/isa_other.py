@@ -12,7 +12,14 @@ compares, selects, lane reads, the division helpers -- is the class OTHER (profi
      a wave runs the block on C2, 64 spp);
   3. prints OTHER per role: static opcodes, executions, wave-instructions per launch, share -- and how the sum compares with the measured
      OTHER total of the committed PMC profile.
-Blocks without a signature of their own are booked under the loop's control flow at one execution per trip: an estimate, labelled so."""
+Blocks without a signature of their own are booked under the loop's control flow at one execution per trip: an estimate, labelled so.
+
+    isa_other.py --cycles [--isa-dir=DIR] [--json]
+prices EVERY VALU opcode of the main loop with the 8-waves-per-SIMD figures of the newest profiles/rNN_valu_rates.json (2.2 cycles for
+f32 add / sub / mul, moves, shifts and two-operand logic, 4.1 for compares, selects, min / max, three-operand integer ops, f64 and
+conversions, 8.1 for sqrt / rcp; a v_cndmask_b32_e32 directly behind another at what tools/cndmask_probe.hip measured for the second
+of such a pair), multiplies by the same executions and prints SIMD cycles per trip by role.  --isa-dir names another build/isa (a
+parent's assembly) for the table before a change."""
 import json
 import os
 import re
@@ -58,9 +65,49 @@ def classify(op):
     return "OTHER"
 
 
-def kernel_body(sub):
+def opcode_costs():
+    """({exact opcode: cycles}, the class costs) from the 8-waves figures of the newest profiles/rNN_valu_rates.json"""
     import glob
-    for path in sorted(glob.glob(os.path.join(ROOT, "build", "isa", "*.s"))):
+    path = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_valu_rates.json")))[-1]
+    ops = json.load(open(path))["results"]["waves_per_simd_8"]["ops"]
+    c = {k: v["cycles"] for k, v in ops.items()}
+    return path, {"two": c["v_add_f32"], "four": c["v_cndmask_b32_e64 (sgpr mask)"], "cmp": c["v_cmp_lt_f32_e64 (sgpr dst)"], "fma": c["v_fma_f32"], "fmac": c["v_fmac_f32"],
+                  "cvt": c["v_cvt_f64_f32 / v_cvt_f32_f64"], "cvt_i": c["v_cvt_f32_i32"], "trans": c["v_sqrt_f32"], "max": c["v_max_f32"]}
+
+
+# what a v_cndmask_b32_e32 directly behind another costs OVER the first (tools/cndmask_probe.hip: "cmp + 2 cndmask e32" 17.13 against "v_cmp vcc +
+# cndmask vcc" 8.09 cycles, profiles/four_cycle_by_role.json); in real code, between other instructions' latencies, an upper bound
+VCC_PAIR_SECOND = 17.13 - 8.09
+
+
+def cycles_of(op, prev, k):
+    """SIMD issue cycles of one VALU opcode at 8 waves per SIMD (k: opcode_costs' classes); prev: the instruction in front of it"""
+    o = re.sub(r"_(e32|e64|dpp|sdwa)$", "", op)
+    if o == "v_cndmask_b32":
+        return VCC_PAIR_SECOND if op.endswith("_e32") and prev.startswith("v_cndmask_b32_e32") else k["four"]
+    if re.match(r"v_(sqrt|rcp|rsq|exp|log|sin|cos)_", o):
+        return k["trans"]
+    if o.endswith("_f64") or re.match(r"v_(cvt_f64|cvt_f32_f64|cvt_i32_f64)", o):
+        return k["cvt"] if o.startswith("v_cvt") else k["four"]
+    if o.startswith("v_cvt"):
+        return k["cvt_i"]
+    if o.startswith("v_cmp"):
+        return k["cmp"]
+    if re.match(r"v_(fma|mad)_f32", o):
+        return k["fma"]
+    if re.match(r"v_(fmac|mac)_f32", o):
+        return k["fmac"]
+    if re.match(r"v_(min|max|min3|max3|med3)_", o) or o.startswith("v_div_") or o.startswith("v_readlane") or o.startswith("v_readfirstlane") or o.startswith("v_writelane"):
+        return k["max"]
+    if re.match(r"v_(add|sub|subrev|mul)_f32$", o) or o in ("v_mov_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_lshlrev_b32", "v_lshrrev_b32", "v_ashrrev_i32",
+                                                          "v_xor_b32", "v_and_b32", "v_or_b32", "v_not_b32", "v_add_co_u32", "v_addc_co_u32"):
+        return k["two"]
+    return k["four"]                               # three-operand integer ops (add3, lshl_add, xad, alignbit, bitop3, bfe ...), mul_lo, everything unlisted
+
+
+def kernel_body(sub, isa_dir=None):
+    import glob
+    for path in sorted(glob.glob(os.path.join(isa_dir or os.path.join(ROOT, "build", "isa"), "*.s"))):
         text = open(path).read()
         for m in re.finditer(r"^(_Z\S*):\s*;?.*?\n(.*?)\.Lfunc_end", text, re.S | re.M):
             name = m.group(1)
@@ -107,7 +154,9 @@ def role_of(b, inner):
     if has("v_cmp_class_f32") and has("v_sqrt_f32"):
         return "sqrt_slow"                         # the compiler's denormal-scaled square root: only when a lane holds 0 < x < 2^-96
     if has("v_min_f32") and has("v_cmp_ngt_f32") and has("v_cmp_gt_u32") and b["valu"] <= 26:
-        return "sphere_test"
+        return "sphere_test"                       # (until the candidates came from two compares: one compare of min(tca, x))
+    if inner and ops.count("v_cmp_ngt_f32_e32") + ops.count("v_cmp_ngt_f32_e64") >= 2 and has("s_and_b64") and has("v_cmp_gt_u32") and b["valu"] <= 26 and not has("v_sqrt_f32"):
+        return "sphere_test"                       # tca < 0 and d2 > r2 as two compares joined by s_and_b64; no v_min_f32, x is the stash's
     valu_ops = [o for o in ops if o.startswith("v_")]
     if inner and b["valu"] == 8 and sorted(o.rsplit("_", 1)[0] for o in valu_ops) == ["v_add_f32"] * 2 + ["v_mul_f32"] * 4 + ["v_sub_f32"] * 2:
         return "sphere_xy"                         # the x-y terms of the sphere test, skipped by a sphere that shares its predecessor's (SphereShare::kXY)
@@ -115,8 +164,9 @@ def role_of(b, inner):
         return "sphere_candidate"                  # a dense pass of the sphere fold: every stashed lane's square root (one copy per sphere site, one behind the walk)
     if inner and b["valu"] == 3 and has("s_and_saveexec_b64") and all(o.startswith("v_mov_b32") for o in ops if o.startswith("v_")):
         return "sphere_stash"                      # a candidate lane keeps (tca, x, index): the masked block behind the sphere test
-    if inner and b["valu"] == 4 and sum(o.startswith("v_cndmask_b32") for o in ops) == 3 and sum(o.startswith("v_mov_b32") for o in ops) == 1:
-        return "sphere_stash"                      # ... the same as three selects and the index's move (render Inline)
+    if inner and b["valu"] in (4, 5) and sum(o.startswith("v_cndmask_b32") for o in ops) == 3 and sum(o.startswith("v_mov_b32") for o in ops) == 1 \
+            and sum(o.startswith("v_sub_f32") for o in ops) == b["valu"] - 4:
+        return "sphere_stash"                      # ... the same as three selects and the index's move (render Inline), with x = r2 - d2 in front of them
     if inner and has("v_cndmask_b32") and has("v_cmp_nle_f32") and b["valu"] <= 8 and not has("v_div_scale_f32"):
         return "sphere_candidate"                  # the fold update behind the square root
     if has("v_div_scale_f32") and (inner or has("v_cmp_nle_f32")):
@@ -155,7 +205,9 @@ def main():
             d = json.load(open(cand))
             measured = (tag, d["mix_wave_instr_per_launch"], d.get("build_id", d.get("source_hash")))
             break
-    name, body = kernel_body("render_inline_kernelILb1ELi8EE")
+    isa_arg = next((a for a in sys.argv[1:] if a.startswith("--isa-dir=")), None)
+    name, body = kernel_body("render_inline_kernelILb1ELi8EE", isa_arg.split("=", 1)[1] if isa_arg else None)
+    rates_path, klass = opcode_costs()
     blocks = blocks_of(body)
     main_header = max(set(h[0] for h in LOOPS.values() if h), key=lambda hd: sum(1 for h in LOOPS.values() if h and h[0] == hd))
     table = []
@@ -165,15 +217,22 @@ def main():
             continue
         counts = dict.fromkeys(CLASSES, 0)
         other_ops = {}
+        cycles, four, prev = 0.0, 0, ""
         for ins in code:
             op = ins.split()[0]
             if op.startswith("v_"):
+                cost = cycles_of(op, prev, klass)
+                cycles += cost
+                four += cost > 3.0 and not op.startswith(("v_sqrt", "v_rcp"))
                 cls = classify(op)
                 counts[cls] += 1
                 if cls == "OTHER":
                     key = re.sub(r"_(e32|e64)$", "", op)
                     other_ops[key] = other_ops.get(key, 0) + 1
-        table.append({"label": label, "code": code, "valu": sum(counts.values()), "counts": counts, "other_ops": other_ops, "inner": len(loops) > 1})
+            if not op.startswith("s_nop") and not op.startswith(";"):
+                prev = op
+        table.append({"label": label, "code": code, "valu": sum(counts.values()), "counts": counts, "other_ops": other_ops, "inner": len(loops) > 1,
+                      "cycles": cycles, "four_cycle": four})
     roles = {}
     order = ["sphere_test", "sphere_xy", "sphere_stash", "sphere_candidate", "plane_test", "sincos3_fast", "sincos_reduce", "sincos_polynomial", "hit_normal", "rest_of_loop", "sqrt_slow", "division_fallback"]
     for b in table:
@@ -233,10 +292,30 @@ def main():
             n_exec = role_execs.get(r)
         dyn = None if n_exec is None else other / copies * n_exec
         dyn_valu = None if n_exec is None else valu / copies * n_exec
+        cyc = sum(b["cycles"] for b in bs)
+        trips = e.get("trips")
         if dyn:
             total += dyn
         out_rows.append({"role": r, "what": what[r], "blocks": len(bs), "copies": copies, "static_valu": valu, "static_other": other, "other_opcodes": ops,
-                         "executions_per_launch": n_exec, "other_wave_instr_per_launch": dyn, "valu_wave_instr_per_launch": dyn_valu})
+                         "executions_per_launch": n_exec, "other_wave_instr_per_launch": dyn, "valu_wave_instr_per_launch": dyn_valu,
+                         "static_cycles": round(cyc, 1), "static_four_cycle_instr": sum(b["four_cycle"] for b in bs),
+                         "cycles_per_execution": round(cyc / copies, 1),
+                         "cycles_per_trip": None if n_exec is None or not trips else round(cyc / copies * n_exec / trips, 1),
+                         "valu_per_trip": None if n_exec is None or not trips else round(valu / copies * n_exec / trips, 1)})
+    if "--cycles" in sys.argv:
+        print("kernel ...%s: main loop %s; opcode costs from %s (8 waves per SIMD); wave-level executions from %s" % (name[-48:], main_header, os.path.relpath(rates_path, ROOT), stats_path))
+        print("%-18s %6s %7s %14s %10s %12s %12s" % ("role", "VALU", "4-cycle", "executions", "cyc / exec", "VALU / trip", "cycles / trip"))
+        for row in out_rows:
+            print("%-18s %6d %7d %14s %10.1f %12s %12s" % (row["role"], row["static_valu"], row["static_four_cycle_instr"],
+                  "%.0f" % row["executions_per_launch"] if row["executions_per_launch"] is not None else "-", row["cycles_per_execution"],
+                  row["valu_per_trip"] if row["valu_per_trip"] is not None else "-", row["cycles_per_trip"] if row["cycles_per_trip"] is not None else "-"))
+        print("sum %.0f VALU instructions and %.0f SIMD cycles per trip (roles with known executions)" % (
+              sum(r["valu_per_trip"] or 0 for r in out_rows), sum(r["cycles_per_trip"] or 0 for r in out_rows)))
+        if "--json" in sys.argv:
+            print(json.dumps({"kernel": name, "main_loop": main_header, "opcode_costs": os.path.relpath(rates_path, ROOT), "wave_block_executions": execs,
+                              "roles": [{k: r[k] for k in ("role", "blocks", "copies", "static_valu", "static_four_cycle_instr", "executions_per_launch", "cycles_per_execution", "valu_per_trip", "cycles_per_trip")} for r in out_rows],
+                              "valu_per_trip": sum(r["valu_per_trip"] or 0 for r in out_rows), "cycles_per_trip": sum(r["cycles_per_trip"] or 0 for r in out_rows)}))
+        return
     print("kernel ...%s: main loop %s, %d blocks; wave-level executions from %s" % (name[-48:], main_header, len(table), stats_path))
     print("%-18s %4s %6s %6s %14s %14s %7s  %s" % ("role", "blk", "VALU", "OTHER", "executions", "OTHER / launch", "share", "OTHER opcodes (static, all copies)"))
     for row in out_rows:

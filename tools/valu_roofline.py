@@ -16,7 +16,10 @@ opcodes), so that
 
 `priced_with_measured_rates` repeats the sum with the per-opcode costs valu_rates measured at 8 waves per SIMD
 (2.2 / 3.6-4.1 / 8.1 cycles: the microbenchmark's own loop control and issue bubbles are inside those figures, so this
-version errs high)."""
+version errs high for the classes the counters name).  It still prices OTHER at v_mov_b32's 2.2 cycles and INT32 at
+v_add_u32's, although OTHER holds the compares, selects and min / max (4.1 cycles each: about half of the class in
+render_inline_kernel's main loop) and INT32 the three-operand integer opcodes: for those two classes it errs LOW.
+tools/isa_other.py --cycles prices the main loop opcode by opcode instead (profiles/four_cycle_by_role.json)."""
 import json
 import os
 import sys
