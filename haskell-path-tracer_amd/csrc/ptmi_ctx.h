@@ -1,5 +1,6 @@
-// ptmi_ctx.h -- what the host units of the C ABI share: the context, its device blocks and the scene's device state (internal; ptmi_api.cpp
-// renders, ptmi_scene.cpp sets, moves and replaces geometry).
+// ptmi_ctx.h -- what the host units of the C ABI share: the context, its device blocks, the scene's device state, the chained closure's
+// states and what the stream form keeps between calls (internal; ptmi_api.cpp renders, ptmi_scene.cpp sets, moves and replaces geometry,
+// ptmi_chain.cpp holds states under tokens, ptmi_stream_call.cpp is the stream form of Streams).
 #pragma once
 
 #include "../../include/ptmi.h"
@@ -97,6 +98,67 @@ struct SceneState {
     }
 };
 
+// The chained closure (ptmi_chain.cpp): the RenderResults the caller holds tokens for.  A state's seven planes are one device block
+// (carve), or -- once it had to make room -- one host block of the same layout.  Blocks of released states wait in free_blocks.
+struct ChainState {
+    uint64_t token = 0;
+    int width = 0, height = 0;
+    DeviceBlock block;                     // planes_bytes(width * height) bytes; empty: the state is on the host
+    std::unique_ptr<char[]> host;          // evicted: as many bytes, carve's layout
+};
+struct ChainStore {
+    std::vector<ChainState> states;        // in token order (oldest first)
+    std::vector<DeviceBlock> free_blocks;
+    uint64_t serial = 0;                   // this context's number in the process: the upper bits of its tokens
+    uint64_t counter = 0;
+    ptmi_chain_stats stats{};
+    template <class F> void each_block(F &&f) { for (ChainState &st : states) f(st.block); for (DeviceBlock &b : free_blocks) f(b); }
+};
+
+// What the stream form of `render Streams` keeps between calls (ptmi_stream_call.cpp).  Everybody else reads `totals` and calls the functions at the end.
+struct StreamFormState {
+    // The tail (ordered_passes): the end of the dispatch order is rendered by the per-pixel kernel on a stream of its own, beside the persistent launch.
+    hipStream_t tail_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // wavefront Streams (scenes with the GLASS extension): two ray streams + {next length, dropped}
+    DeviceBlock queue_block;
+    size_t queue_capacity() const { return queue_block.bytes / (2 * (size_t)kRayQueueWords * 4); }   // ... rays per stream
+    DeviceBlock hit_block;           // the start hits of the pixels, in regions (HitList)
+    // hit_capacity and hit_regions are what the list was LAID OUT for, not what the blocks hold: the block may be larger than
+    // (kHitListWords + 1) * 4 * hit_capacity -- a split-kernel call of R regions at 128 slots each, then an ordered call of 1.5 R regions at
+    // 64 -- and slot_key lies kHitListWords * hit_capacity words into it.
+    size_t hit_capacity = 0;         // ... slots
+    DeviceBlock d_hit_counts;        // ... records per region (unsigned int)
+    DeviceBlock d_hit_missed;        // ... and the pixels of every region that have none (unsigned long long)
+    unsigned int hit_regions = 0;
+    // The start-hit list is a function of (camera, scene, shape, partition, dispatch order) only -- every sample of a pixel
+    // shoots the same primary ray, in every call -- so it is kept until one of them changes.
+    struct HitKey { ptmi_camera cam; uint64_t scene_version, order_generation; int dims[8]; unsigned int region_slots; int cap_allows_split; const void *planes_r; } hit_key{};
+    bool hit_list_valid = false;
+    uint64_t hit_split_pixels = 0;          // pixels whose glass primary hit the list replaced by its children's hits
+    DeviceBlock d_snapshots;         // split kernel: the seed every item starts from
+    DeviceBlock d_region_done;       // ordered passes: items published per region (unsigned int)
+    DeviceBlock d_pass_first;        // split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
+    std::vector<int> pass_first_host;   // ... what the device block holds
+    DeviceBlock d_qcount;            // kLvWords counter words (unsigned int)
+    DeviceBlock spill_block;         // the waves' spill queues
+    int grown_capacity = 0;          // with GLASS: rays per pixel the overflow streams have been GROWN to after a call would have dropped children (0: never)
+    DeviceBlock colour_backup;       // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
+    struct Totals {
+        uint64_t rays_dropped = 0;
+        uint64_t rays_truncated = 0;
+        uint64_t rays_spilled = 0;       // children that found the wave's ring full and went through HBM
+        uint64_t rays_overflowed = 0;    // ... and its spill queue too: traced by an overflow level
+        uint64_t live_host = 0;          // live rays counted on the host
+    } totals;
+    template <class F> void each_block(F &&f) { for (DeviceBlock *b : {&queue_block, &hit_block, &d_hit_counts, &d_hit_missed, &d_snapshots, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup}) f(*b); }
+    int rays_per_pixel(int opt_capacity) const { return grown_capacity > opt_capacity ? grown_capacity : opt_capacity; }   // the capacity in force
+    int forget_streams(ptmi_ctx *c);                 // PTMI_OPT_STREAM_CAPACITY was set: the streams are carved anew, from the value given, by the next call
+    void image_resized();                            // the colour backup was sized by the old image (the caller has drained the stream)
+    void reset_totals() { totals = Totals{}; }
+    void destroy_handles();                          // the tail's events, then its stream (synchronised first)
+};
+
 }  // namespace ptmi
 
 struct ptmi_ctx {
@@ -126,11 +188,7 @@ struct ptmi_ctx {
 
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_snap = nullptr;
-    // The stream form's tail (render_streams_wavefront): the end of the dispatch order is rendered by the per-pixel kernel on a
-    // stream of its own, beside the persistent launch.  d_tail_start: where that end begins (written by the order kernel).
-    hipStream_t tail_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    DeviceBlock d_tail_start;   // unsigned int
+    DeviceBlock d_tail_start;   // unsigned int: where the stream form's tail begins in the dispatch order (written by the order kernel)
     int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
     bool ev_valid = false;
     int variant = ptmi::kVariantAuto;
@@ -140,83 +198,47 @@ struct ptmi_ctx {
     // the order (most expensive first) later launches with the same key use.  order_state = launches made with this key
     DeviceBlock d_quad_cost, d_quad_order, d_quad_class;   // unsigned int per quad
     int order_state = 0;
-    DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup
-    unsigned int chunk_capacity = 0;           // ... that many (the ticket counter's line follows)
+    DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup, then the ticket counter's line
+    unsigned int chunk_capacity() const { return d_chunk_done.bytes ? (unsigned int)(d_chunk_done.bytes / sizeof(unsigned int)) - 32u : 0u; }   // ... that many
     struct OrderKey { ptmi_camera cam; uint64_t scene_version; int dims[8]; } order_key{};
+    uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
 
     // scratch for ptmi_render1 / point queries
     DeviceBlock scratch;
 
-    // wavefront Streams (scenes with the GLASS extension): two ray streams + {next length, dropped}
-    DeviceBlock queue_block;
-    size_t queue_capacity = 0;       // ... rays per stream
-    DeviceBlock hit_block;           // stream form: the start hits of the pixels, in regions (HitList)
-    size_t hit_capacity = 0;         // ... slots
-    DeviceBlock d_hit_counts;        // ... records per region (unsigned int)
-    DeviceBlock d_hit_missed;        // ... and the pixels of every region that have none (unsigned long long)
-    unsigned int hit_regions = 0;
-    // The start-hit list is a function of (camera, scene, shape, partition, dispatch order) only -- every sample of a pixel
-    // shoots the same primary ray, in every call -- so it is kept until one of them changes.
-    struct HitKey { ptmi_camera cam; uint64_t scene_version, order_generation; int dims[8]; unsigned int region_slots; int cap_allows_split; const void *planes_r; } hit_key{};
-    bool hit_list_valid = false;
-    uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
-    uint64_t hit_split_pixels = 0;          // pixels whose glass primary hit the list replaced by its children's hits
-    DeviceBlock d_snapshots;         // stream form, split kernel: the seed every item starts from
     int cus = 0;                     // compute units of the device (persistent grids)
     size_t device_memory = (size_t)64 << 30;   // bytes of the device (budget of the stream form's seed snapshots)
     DeviceBlock tree_stack;          // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
-    DeviceBlock d_region_done;       // stream form, ordered passes: items published per region (unsigned int)
-    int opt_ordered_passes = 0;      // PTMI_OPT_ORDERED_PASSES: 0 = automatic, 1 = off, k = k passes
-    int opt_pass_handoff = 0;        // PTMI_OPT_PASS_HANDOFF: 0 = release / acquire once per (region, pass); 1 = the fence-free write-through hand-off
-    DeviceBlock d_pass_first;        // stream form, split kernel: the samples of every pass (ItemArgs.pass_first), kMaxStreamPasses + 1 entries
-    std::vector<int> pass_first_host;   // ... what the device block holds
-    DeviceBlock d_qcount;            // stream form: kLvWords counter words (unsigned int)
-    uint64_t rays_dropped = 0;
-    uint64_t rays_truncated = 0;
-    uint64_t rays_spilled = 0;       // stream form: children that found the wave's ring full and went through HBM
-    uint64_t rays_overflowed = 0;    // ... and its spill queue too: traced by an overflow level
-    DeviceBlock spill_block;         // stream form: the waves' spill queues
-    uint64_t live_host = 0;        // live rays counted on the host (wavefront path)
+    ptmi::StreamFormState stream_form;   // the stream form's host side (ptmi_stream_call.cpp)
     DeviceBlock d_stream_counters;   // kScWords device counters of the per-pixel Streams kernels
 
     // options of render Streams (ptmi_set_option)
     int opt_seed_rule = PTMI_SEED_AUTO;              // resolved per scene: effective_seed_rule()
     int opt_step_cap = ptmi::kStreamStepCapDefault;
     int opt_capacity = 4;
-    int grown_capacity = 0;                          // stream form with GLASS: rays per pixel the overflow streams have been GROWN to after a call would have dropped children (0: never)
-    DeviceBlock colour_backup;                       // ... the three colour planes as they were before the call's launch (the call is redone if children were dropped)
     int opt_form = PTMI_FORM_AUTO;
     int opt_batch = 0;
     int opt_spp_chunks = 0;                    // 0 = automatic
     int opt_arithmetic = PTMI_ARITH_EXACT;
+    int opt_ordered_passes = 0;      // PTMI_OPT_ORDERED_PASSES: 0 = automatic, 1 = off, k = k passes
+    int opt_pass_handoff = 0;        // PTMI_OPT_PASS_HANDOFF: 0 = release / acquire once per (region, pass); 1 = the fence-free write-through hand-off
     int opt_glass_batch = 0;                   // PTMI_OPT_GLASS_BATCH: 0 = automatic, 1 = off, k = GLASS hits wait until k are pending in their wave
     int opt_graded = 1;                        // PTMI_OPT_STREAM_GRADED: the split kernel's passes shrink towards the end of the launch
     int opt_snapshot_mb = 0;                   // PTMI_OPT_SNAPSHOT_BUDGET_MB: 0 = an eighth of the device's memory
     int opt_pass_groups = 0;                  // PTMI_OPT_STREAM_PASS_GROUPS: 0 = automatic, 1 = off, k = the last k passes are handed out region by region
-
-    // The chained closure (ptmi_render1_chained): the RenderResults the caller holds tokens for.  A state's seven planes are one device
-    // block (carve), or -- once it had to make room -- one host block of the same layout.  Blocks of released states wait in chain_free.
-    struct ChainState {
-        uint64_t token = 0;
-        int width = 0, height = 0;
-        void *block = nullptr;                 // device
-        std::unique_ptr<char[]> host;          // evicted: planes_bytes(n) bytes, carve's layout
-    };
-    std::vector<ChainState> chain;             // in token order (oldest first)
-    std::vector<std::pair<size_t, void *>> chain_free;   // (bytes, device block)
-    uint64_t chain_serial = 0;                 // this context's number in the process: the upper bits of its tokens
-    uint64_t chain_counter = 0;
     int opt_chain_slots = 0;                   // PTMI_OPT_CHAIN_SLOTS: 0 = automatic
-    ptmi_chain_stats chain_stats{};
 
-    // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here.
+    ptmi::ChainStore chain;          // the chained closure's states (ptmi_chain.cpp)
+
+    // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here, or in its owner's each_block.
     template <class F> void each_block(F &&f)
     {
         for (DeviceBlock *b : {&owned_block, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
-                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &queue_block, &hit_block, &d_hit_counts, &d_hit_missed,
-                               &d_snapshots, &tree_stack, &d_region_done, &d_pass_first, &d_qcount, &spill_block, &colour_backup})
+                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &tree_stack})
             f(*b);
         scene.each_block(f);
+        stream_form.each_block(f);
+        chain.each_block(f);
     }
 };
 
@@ -248,5 +270,23 @@ int grow(ptmi_ctx *c, DeviceBlock &b, size_t bytes, const char *what);
 // plain async copies.  copy_to_host leaves the stream drained in both cases.
 hipError_t copy_to_device(ptmi_ctx *c, const CopySpan *spans, int n);
 hipError_t copy_to_host(ptmi_ctx *c, const CopySpan *spans, int n);
+
+// ---- the render path (ptmi_api.cpp), as far as the chain and the stream form use it: seven planes of n pixels in one block, and its size
+Planes carve(void *block, size_t n);
+size_t planes_bytes(size_t n);
+bool too_many_pixels(int width, int height);
+// The planes of n pixels against seven host pointers, as copy spans; a null pointer's plane is skipped (what that means is the caller's to say).  Returns their number.
+int plane_spans(const Planes &p, const void *const host[7], size_t n, CopySpan spans[7]);
+struct RenderTarget {                                      // what a launch renders into: planes, and which rows of which image they are
+    Planes planes;
+    int width, height, rows_local, stripe_rows, n_parts, part;
+    const int64_t *sx, *sy;                                // an explicit screen (ptmi_render1), or null
+    static RenderTarget whole(const Planes &p, int w, int h, const int64_t *sx = nullptr, const int64_t *sy = nullptr) { return {p, w, h, h, h, 1, 0, sx, sy}; }
+};
+int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
+int launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
+constexpr size_t kItersBytes = (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int);      // sharded statistics (ptmi_kernels.h)
+// `render Streams` in its stream form (ptmi_stream_call.cpp): launch_render's branch for it
+int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_camera &camera);
 
 }  // namespace ptmi

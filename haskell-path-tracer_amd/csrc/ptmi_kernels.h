@@ -1,4 +1,4 @@
-// ptmi_kernels.h -- launch interface between the C ABI (ptmi_api.cpp, ptmi_scene.cpp) and the gfx950 kernels (ptmi_*.hip, one unit per kernel family).
+// ptmi_kernels.h -- launch interface between the C ABI (ptmi_api.cpp, ptmi_stream_call.cpp, ptmi_chain.cpp, ptmi_scene.cpp) and the gfx950 kernels (ptmi_*.hip, one unit per kernel family).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -177,7 +177,7 @@ struct ItemArgs {
     unsigned int *chunk_cursor;     // device: the launch's eight ticket counters, kCounterStride words apart, zero at launch
     // streams_split_kernel only
     const int *pass_first;          // device, passes + 1 entries: pass p renders samples [pass_first[p], pass_first[p + 1]) of its pixels -- long items first, short ones
-                                    // at the end of the launch, which is as long as its last items (stream_schedule in ptmi_api.cpp)
+                                    // at the end of the launch, which is as long as its last items (stream_schedule in ptmi_stream_call.cpp)
     const uint4 *seed_snapshots;    // [passes][n_slots]: the seed the item (record slot, pass) starts from (streams_slot_seeds_kernel)
     int glass_batch;                // > 1: GLASS hits wait in their lanes until that many are pending in the wave (PTMI_OPT_GLASS_BATCH)
     unsigned int n_slots;           // slots of the start-hit list: hits.n_regions * hits.region_slots

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(kRenderBlock, PTMI_PIXELS_WAVES) streams_pixel
 
     ChunkCursor cur; cur.home = xcc_id(); cur.tries = 0;
     // (the positions from *tail_start on -- the cheapest quads -- are the per-pixel kernel's, whose waves fill the slots this launch's
-    // waves leave as they end: ptmi_api.cpp)
+    // waves leave as they end: ordered_passes in ptmi_stream_call.cpp)
     cur.n_positions = it.n_positions;
     if (it.tail_start) { const unsigned int t = *it.tail_start; cur.n_positions = t < it.n_positions ? t : it.n_positions; }
     // The wave's next chunk.  Fenced hand-off: the chunk gets a slot for its count of unfinished items; if the slot's previous tenant -- the

@@ -291,6 +291,57 @@ def test_random_walks_over_the_chain_api_equal_a_model_of_values(fresh, pkg, ora
     assert info["evictions"] > 20 and ops["consume"] > 10 and ops["release"] > 10 and ops["from_host"] > 5, (info, ops)
 
 
+def test_states_of_two_image_sizes_make_room_for_each_other(fresh, pkg, ora):
+    """PTMI_OPT_CHAIN_SLOTS = 2 and states of two image sizes held at once: a state of either size leaves the device for one of the other (its
+    block is of no use to the newcomer: freed, and one of the right size allocated), calls render from and consume evicted states of both
+    sizes, and every held token fetches what the model computes for it."""
+    ctx = fresh
+    B = pkg.binding
+    sp, pl = pkg.world.main_scene()
+    cams = [pkg.world.initial_camera(), moved(pkg, pkg.world.initial_camera(), 0.4, -0.07)]
+    size = {"a": (24, 10), "b": (17, 9)}
+    limit = 6
+    ctx.set_scene(sp, pl)
+    ctx.set_option(B.OPT_CHAIN_SLOTS, 2)
+    model, tok = {}, {}                                      # token -> (size, seven planes); name -> token
+
+    def init(name, seed0):
+        w, h = size[name[0]]
+        tok[name] = ctx.chain_init_output(w, h, seed0)
+        model[tok[name]] = (name[0], initial_planes(ora, w, h, seed0))
+
+    def render(name, src, cam, consume=False):
+        w, h = size[src[0]]
+        tok[name], _ = ctx.render1_chained(cams[cam], limit, w, h, tok[src], consume=consume)
+        want, _ = ora.render_inline(sp, pl, cams[cam], w, h, limit, 1, model[tok[src]][1])
+        model[tok[name]] = (src[0], list(want))
+        if consume:
+            del model[tok[src]]
+
+    def on_device():
+        return ctx.chain_info()["states_on_device"]
+
+    init("a0", 11)
+    render("a1", "a0", 0)                                    # device: a0 a1
+    init("b0", 12)                                           # a0 leaves for a state of the other size
+    render("b1", "b0", 1)                                    # a1 leaves: both on the device are of size b
+    render("a2", "a0", 1)                                    # from an evicted state of size a: b0 leaves for it
+    render("a3", "a1", 0, consume=True)                      # consuming an evicted state of size a: b1 leaves
+    render("b2", "b0", 0)                                    # from an evicted state of size b: a2 leaves
+    render("b3", "b1", 1, consume=True)                      # consuming an evicted state of size b: a3 leaves
+    render("a4", "a2", 0)                                    # b2 leaves
+    assert on_device() == 2
+    for t, (s, want) in model.items():
+        assert_planes_equal(ctx.chain_fetch(t, *size[s]), want, "token %x" % t)
+    for gone in ("a1", "b1"):
+        with pytest.raises(pkg.PtmiError) as e:
+            ctx.chain_fetch(tok[gone], *size[gone[0]])
+        assert e.value.code == B.PTMI_ESTALE
+    info = ctx.chain_info()
+    assert len(model) == 7 and info["states_on_device"] + info["states_on_host"] == 7 and info["states_on_device"] == 2
+    assert info["evictions"] == 7 and info["renders_in_place"] == 2, info      # (one state left for every call after the first two)
+
+
 def test_three_threads_share_the_closure_like_the_application(fresh, pkg, ora):
     """app/Main.hs:178-180: a computation thread applies the closure in a loop, the graphics thread reads the colour planes of whatever value
     the MVar holds, a third thread lets old values go -- all on ONE context, entered from three OS threads at once (ctypes drops the GIL
