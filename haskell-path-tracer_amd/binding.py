@@ -134,6 +134,8 @@ SYMBOLS = {
     "ptmi_eval_distance_to_sphere": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_distance_to_plane": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_eval_check_hit": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_trace_rays_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_occluded_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
@@ -254,6 +256,17 @@ def _device_rows(t, words, what):
     if not t.is_cuda or not t.is_contiguous() or "float32" not in str(t.dtype) or t.numel() % words:
         raise ValueError("device %s must be a contiguous float32 tensor of shape (n, %d) on the context's device" % (what, words))
     return _vp(t.data_ptr()), t.numel() // words
+
+
+def _device_tensor(t, dtype, shape, what):
+    """a contiguous device tensor of this dtype ("float32", "int32") and shape, None standing for any length (anything with is_cuda,
+    is_contiguous(), dtype, shape, numel() and data_ptr()) -> its pointer, None for an empty one"""
+    ok = (hasattr(t, "is_cuda") and hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and str(t.dtype).split(".")[-1] == dtype
+          and len(t.shape) == len(shape) and all(want is None or int(got) == want for got, want in zip(t.shape, shape)))
+    if not ok:
+        raise ValueError("%s must be a contiguous %s device tensor of shape (%s) on the context's device"
+                         % (what, dtype, ", ".join("n" if w is None else str(w) for w in shape)))
+    return _vp(t.data_ptr()) if t.numel() else None
 
 
 def mesh_layout(triangles):
@@ -691,6 +704,48 @@ class Context:
         t, idx, just = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.int32)
         self._check(self._lib.ptmi_eval_check_hit(self._h, _ptr(r), n, _ptr(t), _ptr(idx), _ptr(just)))
         return t, idx, just
+
+    # -- ray queries on the device ------------------------------------------------------
+    def trace_rays(self, rays, hit=False, out=None):
+        """ptmi_trace_rays_device: the closest hit of every ray against the current scene, on the context's stream, nothing leaving the
+        device.  rays: a contiguous float32 device tensor of shape (n, 6) -- origin, direction -- anything with is_cuda and data_ptr();
+        the caller orders its writes before the context's stream and keeps the tensors until the stream has passed the call (after
+        set_stream(torch's stream) that stream orders both; on the context's own stream: torch.cuda.synchronize() before the call,
+        synchronize() before the results are read).
+        -> (t, idx), or (t, idx, hit) with hit=True: t float32 (n,), idx int32 (n,) -- spheres, then planes, then triangles; a miss is
+        t 0, idx -1 -- and hit float32 (n, 6), position and normal, zeros for a miss.  They are allocated with torch.empty on the rays'
+        device unless out=(t, idx) or out=(t, idx, hit) gives the caller's own."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        if out is not None:
+            if len(out) not in (2, 3):
+                raise ValueError("out must be (t, idx) or (t, idx, hit)")
+            hit = len(out) == 3
+            outs = tuple(out)
+        else:
+            import torch
+            outs = (torch.empty(n, dtype=torch.float32, device=rays.device), torch.empty(n, dtype=torch.int32, device=rays.device))
+            if hit:
+                outs += (torch.empty((n, 6), dtype=torch.float32, device=rays.device),)
+        d_t = _device_tensor(outs[0], "float32", (n,), "t")
+        d_idx = _device_tensor(outs[1], "int32", (n,), "idx")
+        d_hit = _device_tensor(outs[2], "float32", (n, 6), "hit") if hit else None
+        self._check(self._lib.ptmi_trace_rays_device(self._h, d_rays, n, d_t, d_idx, d_hit))
+        return outs
+
+    def occluded(self, rays, t_max, out=None):
+        """ptmi_occluded_device: 1 where the closest hit of a ray is nearer than its t_max, else 0 (a NaN or non-positive t_max: 0), found
+        by an any-hit walk on the context's stream.  rays as trace_rays takes them, t_max a contiguous float32 device tensor of shape
+        (n,) -> an int32 device tensor (n,): `out`, or one allocated with torch.empty on the rays' device."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        d_t_max = _device_tensor(t_max, "float32", (n,), "t_max")
+        if out is None:
+            import torch
+            out = torch.empty(n, dtype=torch.int32, device=rays.device)
+        d_out = _device_tensor(out, "int32", (n,), "out")
+        self._check(self._lib.ptmi_occluded_device(self._h, d_rays, d_t_max, n, d_out))
+        return out
 
     def eval_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

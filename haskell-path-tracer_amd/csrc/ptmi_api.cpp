@@ -934,6 +934,44 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     return PTMI_OK;
 }
 
+// The ray queries on the caller's device arrays: refusals first (nothing enqueued, nothing written), then one launch on the context's
+// stream -- no synchronisation, no allocation, no scratch.
+static SceneView query_scene(const ptmi_ctx *c)
+{
+    SceneView scene;
+    scene.packed = c->scene.packed.as<float4>(); scene.n_spheres = (int)c->scene.rows.ns; scene.n_planes = (int)c->scene.rows.np;
+    scene.share_xy = c->scene.share_xy;
+    return scene;
+}
+
+int ptmi_trace_rays_device(ptmi_ctx *c, const float *d_rays, int n, float *d_t, int32_t *d_idx, float *d_hit)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!d_rays || !d_t || !d_idx))) return fail(c, PTMI_EINVAL, "bad ray-query arguments");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (n == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const SceneState &s = c->scene;
+    PTMI_HIP(c, launch_trace_rays(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
+                                  d_t, d_idx, d_hit, c->stream));
+    return PTMI_OK;
+}
+
+int ptmi_occluded_device(ptmi_ctx *c, const float *d_rays, const float *d_t_max, int n, int32_t *d_occluded)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!d_rays || !d_t_max || !d_occluded))) return fail(c, PTMI_EINVAL, "bad ray-query arguments");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (n == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const SceneState &s = c->scene;
+    PTMI_HIP(c, launch_occluded(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, s.sphere_reach,
+                                d_rays, d_t_max, n, d_occluded, c->stream));
+    return PTMI_OK;
+}
+
 int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *cos_out)
 {
     if (!c) return PTMI_EINVAL;

@@ -12,6 +12,24 @@ namespace {
 
 constexpr int kBvhStack = PTMI_BVH_MAX_DEPTH;   // entries of a lane's traversal stack: at a node of level k at most k are held
 
+// The arithmetic of the walks' box tests (the comment below says what it is for).  Macros, as PTMI_SPHERE_TEST is one, so that every walk
+// -- check_hit_bvh, check_hit_mesh's two, the any-hit walks of ptmi_query_device.h -- makes the SAME operations and each keeps its code.
+//   PTMI_SLAB_REACH     e = box centre - origin, and the L1 norm p1 and the squared L2 norm p2 of |e| + h: declares ex, ey, ez, p1, p2
+//   PTMI_SPHERE_MARGIN  the margin m of a child of the sphere hierarchy (G, G_lin and sqrt_G are the walk's)
+//   PTMI_SLAB_TEST      the slab test of the box widened by m: assigns t_near, declares t_far
+#define PTMI_SLAB_REACH(c, h, o)                                                                                                    \
+    const float ex = c.x - o.x, ey = c.y - o.y, ez = c.z - o.z;                                                                     \
+    const float ax = __builtin_fabsf(ex) + h.x, ay = __builtin_fabsf(ey) + h.y, az = __builtin_fabsf(ez) + h.z;                     \
+    const float p1 = (ax + ay) + az, p2 = (ax * ax + ay * ay) + az * az
+#define PTMI_SPHERE_MARGIN(p1, p2, inv_2r) \
+    (((__builtin_fminf(sqrt_G * p1, (G * p2) * inv_2r) + G_lin * p1) + 0x1p-30f) * (1.0f + 0x1p-10f))
+#define PTMI_SLAB_TEST(h, m, inv, ainv, far, t_near)                                                                                \
+    const float tmx = ex * inv.x, hx = (h.x + m) * ainv.x;                                                                          \
+    const float tmy = ey * inv.y, hy = (h.y + m) * ainv.y;                                                                          \
+    const float tmz = ez * inv.z, hz = (h.z + m) * ainv.z;                                                                          \
+    t_near = __builtin_fmaxf(__builtin_fmaxf(tmx - hx, tmy - hy), __builtin_fmaxf(tmz - hz, 0.0f));                                 \
+    const float t_far = __builtin_fminf(__builtin_fminf(tmx + hx, tmy + hy), tmz + hz) * far
+
 // check_hit_bvh returns what check_hit returns, bit for bit:
 //   * SAME ARITHMETIC: every sphere it tests is tested by check_hit's operations (sqrt_rn included);
 //   * SAME CHOICE: among the spheres the minimum of (key, original index) -- for finite keys the left fold's first minimum -- then the
@@ -66,15 +84,9 @@ __device__ __forceinline__ HitSel check_hit_bvh(const BvhView &B, ScenePtr S, in
         // distance is the child's own: |centre - origin| <= |c - o| + h per axis for every sphere in the box (p1 its L1 norm, p2 the
         // square of its L2 norm), so near boxes -- where bounce rays spend their tests -- get a near-zero margin.
         auto slab = [&](V3 c, V3 h, float inv_2r, float &t_near) {
-            const float ex = c.x - o.x, ey = c.y - o.y, ez = c.z - o.z;
-            const float ax = __builtin_fabsf(ex) + h.x, ay = __builtin_fabsf(ey) + h.y, az = __builtin_fabsf(ez) + h.z;
-            const float p1 = (ax + ay) + az, p2 = (ax * ax + ay * ay) + az * az;
-            const float m = ((__builtin_fminf(sqrt_G * p1, (G * p2) * inv_2r) + G_lin * p1) + 0x1p-30f) * (1.0f + 0x1p-10f);
-            const float tmx = ex * inv.x, hx = (h.x + m) * ainv.x;
-            const float tmy = ey * inv.y, hy = (h.y + m) * ainv.y;
-            const float tmz = ez * inv.z, hz = (h.z + m) * ainv.z;
-            t_near = __builtin_fmaxf(__builtin_fmaxf(tmx - hx, tmy - hy), __builtin_fmaxf(tmz - hz, 0.0f));
-            const float t_far = __builtin_fminf(__builtin_fminf(tmx + hx, tmy + hy), tmz + hz) * kFar;
+            PTMI_SLAB_REACH(c, h, o);                        // ex, ey, ez, p1, p2
+            const float m = PTMI_SPHERE_MARGIN(p1, p2, inv_2r);
+            PTMI_SLAB_TEST(h, m, inv, ainv, kFar, t_near);   // t_near, t_far
             return t_near <= t_far;
         };
         auto leaf = [&](int32_t ref) {

@@ -82,6 +82,7 @@ struct SceneState {
     DeviceBlock packed, packed_shadow;                     // PackedRows; the second block is the sphere refit's, beside spheres.shadow
     PackedRows rows;
     uint64_t share_xy = 0;                                 // a linear scene's spheres that repeat their predecessor's (cx, cy) bits (ptmi_share.h); else 0
+    float sphere_reach = 0.0f;                             // a linear scene's largest |sphere centre component| or r^2, +inf when one is not finite: what the any-hit walk may assume (ptmi_query_device.h)
     Hierarchy<SphereLayout> spheres;                       // a BVH or mesh scene
     Hierarchy<MeshLayout> triangles;                       // a mesh scene
     bool glass_spheres = false, glass_planes = false, glass_triangles = false;

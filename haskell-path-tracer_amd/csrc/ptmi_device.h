@@ -6,6 +6,7 @@
 //   ptmi_streams_tree.hip    render Streams with ray splitting, one tree per pixel
 //   ptmi_stream_primary.hip / ptmi_stream_pixels.hip / ptmi_stream_split.hip   the stream ("wavefront") form (ptmi_stream_form.h)
 //   ptmi_small.hip           seeds, createWith, present, stitch, dispatch order, point queries
+//   ptmi_query.hip           the ray queries on device-resident rays: closest hit, occlusion (ptmi_query_device.h)
 // Everything here is in an unnamed namespace: each unit gets its own copy, nothing is linked across units (no -fgpu-rdc).
 // Diagnostic builds (-DPTMI_*_STATS) live in ptmi_diag.h; the kernels only call its probes, which are empty otherwise.
 #pragma once
@@ -159,6 +160,14 @@ __device__ __noinline__ HitSel check_hit_exact(ScenePtr S, int ns, int np, V3 o,
 //     element (see check_hit): it differs from the literal fold only where the final accumulator is a Just whose key is not < FLT_MAX
 //     -- which the callers detect and redo literally -- or where the accumulator is never filled (no sphere on the square-root path,
 //     no pass): just == false then, as in the literal fold, and every caller reads t and idx of a Just only.
+// The per-plane operations of that fold, for it and for the any-hit walks (ptmi_query_device.h); macros for PTMI_SPHERE_TEST's reason.
+// PTMI_PLANE_DENOM: the denominator of a plane's normal row; PTMI_PLANE_DISTANCE: for the plane (gp, gn) and the denominator the lane
+// kept, declares t and just.
+#define PTMI_PLANE_DENOM(gn, d) dot(d, mk(gn.x, gn.y, gn.z))
+#define PTMI_PLANE_DISTANCE(gp, gn, o, denom)                                                                                       \
+    const float t = dot(mk(gp.x, gp.y, gp.z) - o, mk(gn.x, gn.y, gn.z)) / denom;                                                    \
+    const bool just = !(denom > 1e-6f) && !(t < 0.0f)
+
 template <typename At>
 __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, float &best_key, int &best_idx, bool &best_just,
                                             unsigned int *diag = nullptr)
@@ -169,8 +178,7 @@ __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, f
     auto pass = [&]() {
         diag::plane_pass(diag);
         const float4 gp = at(2 * stash), gn = at(2 * stash + 1);
-        const float t = dot(mk(gp.x, gp.y, gp.z) - o, mk(gn.x, gn.y, gn.z)) / stash_denom;
-        const bool just = !(stash_denom > 1e-6f) && !(t < 0.0f);
+        PTMI_PLANE_DISTANCE(gp, gn, o, stash_denom);         // t, just
         const float key = just ? t : kInfinite;
         if (!(best_key <= key)) { best_key = key; best_idx = ns + stash; best_just = just; }
         stash_denom = 1.0f;
@@ -178,7 +186,7 @@ __device__ __forceinline__ void fold_planes(At at, int ns, int np, V3 o, V3 d, f
     };
     for (int j = 0; j < np; ++j) {
         const float4 gn = at(2 * j + 1);
-        const float denom = dot(d, mk(gn.x, gn.y, gn.z));
+        const float denom = PTMI_PLANE_DENOM(gn, d);
         const bool cand = !(denom > 1e-6f);
         const unsigned long long cands = __ballot(cand);
         diag::plane_test(diag);

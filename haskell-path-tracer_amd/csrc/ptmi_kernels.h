@@ -261,6 +261,14 @@ hipError_t launch_render_inline_mesh(const RenderArgs &a, const MeshView &mesh, 
 hipError_t launch_render_streams_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
 hipError_t launch_render_streams_tree_mesh(const RenderArgs &a, const MeshView &mesh, hipStream_t stream);
 hipError_t launch_eval_check_hit_mesh(SceneView scene, const MeshView &mesh, const float *rays, int n, float *t, int32_t *idx, int32_t *just, hipStream_t stream);
+// The ray queries on device-resident arrays (ptmi_trace_rays_device, ptmi_occluded_device; ptmi_query.hip): one lane per ray against a linear
+// scene (bvh and mesh null; its shared-xy walk when scene.share_xy is not 0), a BVH scene (bvh) or a mesh scene (mesh).  hit: n x 6 words or
+// null.  reach: a linear scene's largest |sphere centre component| or r^2, +inf when one is not finite (SceneState.sphere_reach).  Every
+// array needs 4-byte alignment; 8-byte aligned rays and hit records are moved two words at a time.
+hipError_t launch_trace_rays(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, int n, float *t, int32_t *idx, float *hit,
+                             hipStream_t stream);
+hipError_t launch_occluded(SceneView scene, const BvhView *bvh, const MeshView *mesh, float reach, const float *rays, const float *t_max, int n,
+                           int32_t *occluded, hipStream_t stream);
 // Moving a mesh scene's vertices (ptmi_update_mesh_vertices; ptmi_mesh_refit.hip).  vertices: 9 floats per triangle by original index, device
 // memory; leaf_pos: per triangle its position in the leaf order or -1; result: kRefitWords words (ptmi_mesh_box.h), all ones in
 // [0, kRefitHi), zero behind, at launch.  check writes `result` only; records writes both copies of the records; level the boxes of

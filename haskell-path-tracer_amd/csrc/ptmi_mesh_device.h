@@ -45,6 +45,10 @@ __device__ __forceinline__ float bvh_inv_of(float v)
 }
 constexpr float kBvhFar = 1.0f + 2.0f * (3.0f * 0x1p-24f) / (1.0f - 3.0f * 0x1p-24f);     // 1 + 2 gamma_3
 
+// The margin m of a child of the TRIANGLE hierarchy (check_hit_mesh's comment says why): p1 as PTMI_SLAB_REACH declares it, o1 the L1 norm
+// of the origin.  A macro for the reason the slab's are (ptmi_bvh_device.h).
+#define PTMI_MESH_MARGIN(p1, o1) (((p1 + o1) * 0x1p-16f + 0x1p-30f) * (1.0f + 0x1p-10f))
+
 // The sphere walk: the minimum of (key, original index) over the spheres into (best_key, best_idx, best_just), which start as
 // (kInfinite, 0x7fffffff, false)
 __device__ __forceinline__ void bvh_walk_spheres(const BvhView &B, uint32_t *col, V3 o, V3 d, float eta, float &best_key, int &best_idx, bool &best_just)
@@ -61,15 +65,9 @@ __device__ __forceinline__ void bvh_walk_spheres(const BvhView &B, uint32_t *col
         // distance is the child's own: |centre - origin| <= |c - o| + h per axis for every sphere in the box (p1 its L1 norm, p2 the
         // square of its L2 norm), so near boxes -- where bounce rays spend their tests -- get a near-zero margin.
         auto slab = [&](V3 c, V3 h, float inv_2r, float &t_near) {
-            const float ex = c.x - o.x, ey = c.y - o.y, ez = c.z - o.z;
-            const float ax = __builtin_fabsf(ex) + h.x, ay = __builtin_fabsf(ey) + h.y, az = __builtin_fabsf(ez) + h.z;
-            const float p1 = (ax + ay) + az, p2 = (ax * ax + ay * ay) + az * az;
-            const float m = ((__builtin_fminf(sqrt_G * p1, (G * p2) * inv_2r) + G_lin * p1) + 0x1p-30f) * (1.0f + 0x1p-10f);
-            const float tmx = ex * inv.x, hx = (h.x + m) * ainv.x;
-            const float tmy = ey * inv.y, hy = (h.y + m) * ainv.y;
-            const float tmz = ez * inv.z, hz = (h.z + m) * ainv.z;
-            t_near = __builtin_fmaxf(__builtin_fmaxf(tmx - hx, tmy - hy), __builtin_fmaxf(tmz - hz, 0.0f));
-            const float t_far = __builtin_fminf(__builtin_fminf(tmx + hx, tmy + hy), tmz + hz) * kFar;
+            PTMI_SLAB_REACH(c, h, o);                        // ex, ey, ez, p1, p2
+            const float m = PTMI_SPHERE_MARGIN(p1, p2, inv_2r);
+            PTMI_SLAB_TEST(h, m, inv, ainv, kFar, t_near);   // t_near, t_far
             return t_near <= t_far;
         };
         auto leaf = [&](int32_t ref) {
@@ -146,9 +144,14 @@ __device__ __forceinline__ void bvh_fold_planes(ScenePtr S, int ns, int np, V3 o
 
 // The fold over spheres ++ planes ++ triangles written out literally (every primitive in order, a Nothing keyed FLT_MAX): what the
 // hierarchy gives up on -- a ray it does not serve, a final key that is not < FLT_MAX.  A triangle of zero area (NaN normal) is a Nothing.
-// (Not inlined: it calls check_hit_exact, so its frame -- 16 bytes of scratch in every mesh kernel -- holds the return address.)
+// (Not inlined: it calls check_hit_exact, so its frame -- 16 bytes of scratch in every mesh kernel -- holds the return address.  A unit
+// whose kernels have the registers to spare defines PTMI_MESH_EXACT_INLINE as __forceinline__ before it includes this header: the fold is
+// then part of the kernel, calls check_hit_exact as a leaf and needs no frame -- ptmi_query.hip, whose kernels LDS holds to four waves.)
+#ifndef PTMI_MESH_EXACT_INLINE
+#define PTMI_MESH_EXACT_INLINE __noinline__
+#endif
 template <typename ScenePtr>
-__device__ __noinline__ HitSel check_hit_mesh_exact(const float4 *by_index, int n_triangles, ScenePtr S, int ns, int np, V3 o, V3 d)
+__device__ PTMI_MESH_EXACT_INLINE HitSel check_hit_mesh_exact(const float4 *by_index, int n_triangles, ScenePtr S, int ns, int np, V3 o, V3 d)
 {
     HitSel best = check_hit_exact(S, ns, np, o, d);
     float best_key = best.just ? best.t : kInfinite;
@@ -196,15 +199,10 @@ __device__ __forceinline__ HitSel check_hit_mesh(const MeshView &M, ScenePtr S, 
         // the bound a child's entry distance is held to: the accumulator's key, or everything while it holds no key (NaN)
         auto bound = [&]() { return best_key == best_key ? best_key : kInfinite; };
         auto slab = [&](V3 c, V3 h, float &t_near) {
-            const float ex = c.x - o.x, ey = c.y - o.y, ez = c.z - o.z;
-            const float ax = __builtin_fabsf(ex) + h.x, ay = __builtin_fabsf(ey) + h.y, az = __builtin_fabsf(ez) + h.z;
-            const float p1 = (ax + ay) + az;
-            const float m = ((p1 + o1) * 0x1p-16f + 0x1p-30f) * (1.0f + 0x1p-10f);
-            const float tmx = ex * inv.x, hx = (h.x + m) * ainv.x;
-            const float tmy = ey * inv.y, hy = (h.y + m) * ainv.y;
-            const float tmz = ez * inv.z, hz = (h.z + m) * ainv.z;
-            t_near = __builtin_fmaxf(__builtin_fmaxf(tmx - hx, tmy - hy), __builtin_fmaxf(tmz - hz, 0.0f));
-            const float t_far = __builtin_fminf(__builtin_fminf(tmx + hx, tmy + hy), tmz + hz) * kBvhFar;
+            PTMI_SLAB_REACH(c, h, o);                        // ex, ey, ez, p1 (p2 is the sphere walk's)
+            (void)p2;
+            const float m = PTMI_MESH_MARGIN(p1, o1);
+            PTMI_SLAB_TEST(h, m, inv, ainv, kBvhFar, t_near);   // t_near, t_far
             return t_near <= t_far;
         };
         auto leaf = [&](int32_t ref) {

@@ -4,6 +4,7 @@
 // before that leaves the scene it found: the candidate's destructor frees what was made.
 #include "ptmi_ctx.h"
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,7 @@ struct Candidate {
     DeviceBlock packed, packed_shadow;
     PackedRows rows;
     uint64_t share_xy = 0;                                 // of `packed` (shared_xy_mask, ptmi_share.h): a linear scene's; 0 for the hierarchies
+    float sphere_reach = 0.0f;                             // of `packed`, a linear scene's (sphere_reach_of); the hierarchies have their boxes
     Hierarchy<SphereLayout> spheres;                       // block, plan (and, a refit's first, shadow) with their layouts, levels and box
     Hierarchy<MeshLayout> triangles;                       // block, shadow, plan
     bool refit_spheres = false, refit_triangles = false;   // the second blocks were written: they swap with the scene's (the boxes are new)
@@ -107,7 +109,7 @@ void commit(Candidate &k)
     if (k.packed.p || k.spheres.block.p) { release(s.packed_shadow); release(s.spheres.shadow); }
     if (k.packed.p) { take(s.packed, k.packed); s.rows = k.rows; }
     // the sharing mask is the packed block's: whatever replaces the block (or the whole scene) replaces the mask, so none outlives its spheres
-    if (k.packed.p || k.whole) s.share_xy = k.share_xy;
+    if (k.packed.p || k.whole) { s.share_xy = k.share_xy; s.sphere_reach = k.sphere_reach; }
     if (k.spheres.block.p) take_tree(s.spheres, k.spheres);
     // (the mesh refit's second block comes with the block it copies)
     if (k.triangles.block.p) { take_tree(s.triangles, k.triangles); take(s.triangles.shadow, k.triangles.shadow); }
@@ -183,6 +185,16 @@ void pack_scene(const PackedRows &rows, const ptmi_sphere *sph, const ptmi_plane
     for (size_t i = 0; i < rows.ns; ++i) mat(sph[i].color, sph[i].illuminance, sph[i].brdf_tag, sph[i].brdf_param);
     for (size_t j = 0; j < rows.np; ++j) mat(pl[j].color, pl[j].illuminance, pl[j].brdf_tag, pl[j].brdf_param);
     for (size_t t = 0; t < rows.nt; ++t) mat(tri[t].color, tri[t].illuminance, tri[t].brdf_tag, tri[t].brdf_param);
+}
+
+// The largest magnitude among the sphere rows (cx, cy, cz, r * r) of a packed linear scene, +inf when one of them is not finite
+float sphere_reach_of(const float4 *rows, int n_spheres)
+{
+    float reach = 0.0f;
+    for (int i = 0; i < n_spheres; ++i)
+        for (float v : {rows[i].x, rows[i].y, rows[i].z, rows[i].w})
+            reach = std::isfinite(v) ? std::fmax(reach, std::fabs(v)) : INFINITY;
+    return reach;
 }
 
 // The sphere hierarchy of a host build: its block (nodes, the spheres in leaf order as pack_scene makes them, their indices) and its plan
@@ -522,6 +534,7 @@ int ptmi_set_scene(ptmi_ctx *c, const ptmi_sphere *spheres, int n_spheres, const
     std::vector<float4> packed;
     pack_scene(k.rows, spheres, planes, nullptr, packed);
     k.share_xy = shared_xy_mask(&packed[0].x, 4, n_spheres);  // of the rows the kernels read
+    k.sphere_reach = sphere_reach_of(packed.data(), n_spheres);
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     // the new scene stands complete before the old one goes
     k.alloc(k.packed, k.rows.bytes());

@@ -50,7 +50,8 @@ extern "C" {
                             * (ptmi_update_spheres, ptmi_update_spheres_device, ptmi_set_bvh_spheres, ptmi_set_bvh_spheres_device,
                             * ptmi_group_update_spheres, ptmi_group_set_bvh_spheres, ptmi_bvh_refit_layout, ptmi_bvh_layout_morton,
                             * ptmi_bvh_read_layout); the spatial device build of a sphere hierarchy (option 17 = PTMI_OPT_BVH_DEVICE_BUILD,
-                            * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial). */
+                            * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial); the ray queries on device-resident rays (ptmi_trace_rays_device,
+                            * ptmi_occluded_device). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -724,6 +725,34 @@ int ptmi_group_get_stats(ptmi_group *group, ptmi_stats *sum);  /* sums (maxima f
 /* The partition's arithmetic, usable without a device: rows part `part` holds, and the image row of one of them. */
 int ptmi_partition_rows(int height, int stripe_rows, int n_parts, int part);
 int ptmi_partition_global_row(int height, int stripe_rows, int n_parts, int part, int local_row);
+
+/* ---- ray queries on the device ------------------------------------------------ */
+/* The caller's own rays against the context's current scene -- linear, BVH or mesh -- without leaving the device: closest hit with its hit
+ * record, and occlusion before a distance (shadow and visibility rays, range sensors).  d_rays: n x 6 floats (origin, direction), as
+ * ptmi_eval_check_hit takes them, in device memory of the context's device, like every other array here; each needs 4-byte alignment only
+ * (8-byte aligned rays and hit records are moved two words at a time).
+ *   - ORDER AND LIFETIME.  One launch on the context's launch stream (ptmi_set_stream), and nothing else: no host synchronisation, no
+ *     device allocation, no staging.  The caller orders its writes to the inputs before that stream (they are on it, or an event makes it
+ *     wait), keeps every array alive until the stream has passed the call, and reads the outputs behind the stream.  A later scene call on
+ *     the same context -- a move, a refit, a replacement, another scene -- is ordered behind the query: the query answers for the scene as
+ *     it stood at the call, and a query enqueued after an update answers for the updated scene.
+ *   - ptmi_trace_rays_device: d_t[i] and d_idx[i] are ptmi_eval_check_hit's t_out[i] and idx_out[i] for ray i, bit for bit (the same
+ *     device functions): the primitive by the existing convention, spheres, then planes, then triangles; a miss is t = 0, idx = -1, so
+ *     idx >= 0 says Just.  d_hit, unless NULL, receives n x 6 floats: the hit position o + d ^* t and the normal of the selected primitive
+ *     as the render kernels compute them (a sphere's normalised (p - centre), a plane's stored direction, a triangle's unit normal); six
+ *     zeros for a miss.
+ *   - ptmi_occluded_device: d_occluded[i] = 1 if the closest hit of ray i is a Just and its t < d_t_max[i] (one binary32 compare against
+ *     that same closest hit), else 0.  So a NaN or non-positive t_max gives 0, and +inf asks whether the ray hits anything at a finite t.
+ *     It is computed by an any-hit walk that stops at the first primitive that decides the answer and enters no box beyond t_max; where
+ *     that would not provably equal the definition -- a ray the hierarchies do not serve, a plane whose key is not finite -- the lane
+ *     takes the closest-hit search and compares (csrc/ptmi_query_device.h has the argument, DESIGN.md 5.9 the measurements).
+ *   - Refusals enqueue and write nothing: PTMI_ESTATE before any scene is set; PTMI_EINVAL for a negative n and for a NULL required
+ *     pointer with n > 0 (d_hit may be NULL).  n == 0 is PTMI_OK and touches nothing.  The pointers are not inspected: an address that
+ *     is not device memory of the context's device fails as any kernel's would.
+ *   - There is no group form: a group's members are different devices and an array of rays lives on one.  Query a member
+ *     (ptmi_group_member) with rays on its device. */
+int ptmi_trace_rays_device(ptmi_ctx *ctx, const float *d_rays, int n, float *d_t, int32_t *d_idx, float *d_hit /* [n][6] position, normal; may be NULL */);
+int ptmi_occluded_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, int32_t *d_occluded);
 
 /* ---- point queries (the reference's unit-test surface) ------------------------ */
 /* Evaluates distanceTo / hit (src/Scene/Intersection.hs:16-64) on the DEVICE for n independent
