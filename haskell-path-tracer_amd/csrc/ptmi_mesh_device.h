@@ -10,118 +10,6 @@ namespace ptmi {
 
 namespace {
 
-// check_hit_bvh's parts (ptmi_bvh_device.h), as functions that check_hit_mesh runs on ONE stack: the sphere walk and the plane fold are
-// check_hit_bvh's text operation for operation (check_hit_bvh itself stays as it is, so that the BVH kernels keep their code).
-__device__ __forceinline__ uint32_t *bvh_stack_column()
-{
-    __shared__ uint32_t bvh_stack[kBvhStack][kRenderBlock];
-    return &bvh_stack[0][threadIdx.x % kRenderBlock];
-}
-
-// What the lane's ray may take from the hierarchy: eta = | |d|^2 - 1 |, P >= the distance from the origin to the box (lo, hi)
-__device__ __forceinline__ float bvh_eta(V3 d) { return __builtin_fabsf(dot(d, d) - 1.0f); }
-__device__ __forceinline__ float bvh_reach(const float lo[3], const float hi[3], V3 o)
-{
-    float P2 = 0.0f;
-    const float oc[3] = {o.x, o.y, o.z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pa = __builtin_fmaxf(__builtin_fabsf(lo[a] - oc[a]), __builtin_fabsf(hi[a] - oc[a]));
-        P2 = P2 + pa * pa;
-    }
-    return __builtin_sqrtf(P2) * (1.0f + 0x1p-20f);
-}
-__device__ __forceinline__ bool bvh_ray_finite(V3 o, V3 d)
-{
-    return __builtin_isfinite(o.x) && __builtin_isfinite(o.y) && __builtin_isfinite(o.z) &&
-           __builtin_isfinite(d.x) && __builtin_isfinite(d.y) && __builtin_isfinite(d.z);
-}
-
-// 1 / d per component, |component| taken as at least 2^-80 (see above)
-__device__ __forceinline__ float bvh_inv_of(float v)
-{
-    const float c = __builtin_fabsf(v) < 0x1p-80f ? __builtin_copysignf(0x1p-80f, v) : v;
-    return 1.0f / c;
-}
-constexpr float kBvhFar = 1.0f + 2.0f * (3.0f * 0x1p-24f) / (1.0f - 3.0f * 0x1p-24f);     // 1 + 2 gamma_3
-
-// The margin m of a child of the TRIANGLE hierarchy (check_hit_mesh's comment says why): p1 as PTMI_SLAB_REACH declares it, o1 the L1 norm
-// of the origin.  A macro for the reason the slab's are (ptmi_bvh_device.h).
-#define PTMI_MESH_MARGIN(p1, o1) (((p1 + o1) * 0x1p-16f + 0x1p-30f) * (1.0f + 0x1p-10f))
-
-// The sphere walk: the minimum of (key, original index) over the spheres into (best_key, best_idx, best_just), which start as
-// (kInfinite, 0x7fffffff, false)
-__device__ __forceinline__ void bvh_walk_spheres(const BvhView &B, uint32_t *col, V3 o, V3 d, float eta, float &best_key, int &best_idx, bool &best_just)
-{
-    {
-        const float G = 0x1p-19f + 2.0f * eta, G_lin = G + 0x1p-19f, sqrt_G = __builtin_sqrtf(G);
-        auto inv_of = [](float v) { return bvh_inv_of(v); };
-        const V3 inv = mk(inv_of(d.x), inv_of(d.y), inv_of(d.z));
-        const V3 ainv = mk(__builtin_fabsf(inv.x), __builtin_fabsf(inv.y), __builtin_fabsf(inv.z));
-        constexpr float kFar = kBvhFar;
-
-
-        // entry distance of a child's box (NaN-free operations ignore a NaN operand: a degenerate axis never prunes).  The margin's
-        // distance is the child's own: |centre - origin| <= |c - o| + h per axis for every sphere in the box (p1 its L1 norm, p2 the
-        // square of its L2 norm), so near boxes -- where bounce rays spend their tests -- get a near-zero margin.
-        auto slab = [&](V3 c, V3 h, float inv_2r, float &t_near) {
-            PTMI_SLAB_REACH(c, h, o);                        // ex, ey, ez, p1, p2
-            const float m = PTMI_SPHERE_MARGIN(p1, p2, inv_2r);
-            PTMI_SLAB_TEST(h, m, inv, ainv, kFar, t_near);   // t_near, t_far
-            return t_near <= t_far;
-        };
-        auto leaf = [&](int32_t ref) {
-            const uint32_t v = (uint32_t)(-1 - ref);
-            const int first = (int)(v >> 8), count = (int)(v & 255u);
-            for (int k = 0; k < count; ++k) {
-                const float4 g = B.geom[first + k];
-                const int i = B.index[first + k];
-                PTMI_SPHERE_TEST(g, o, d);                   // check_hit's sphere test (ptmi_device.h): tca, x, cand
-                const float t = tca - sqrt_rn(x);
-                const bool just = cand && !(t < 0.0f);
-                if (just && (t < best_key || (t == best_key && i < best_idx))) { best_key = t; best_idx = i; best_just = true; }
-            }
-        };
-
-        int node = 0, sp = 0;
-        while (true) {
-            const float4 f0 = B.nodes[4 * node], f1 = B.nodes[4 * node + 1], f2 = B.nodes[4 * node + 2], f3 = B.nodes[4 * node + 3];
-            const int32_t r0 = (int32_t)f2u(f3.x), r1 = (int32_t)f2u(f3.y);
-            float t0, t1;
-            const bool h0 = slab(mk(f0.x, f0.y, f0.z), mk(f1.z, f1.w, f2.x), f3.z, t0) && r0 != -1 && t0 <= best_key;
-            const bool h1 = slab(mk(f0.w, f1.x, f1.y), mk(f2.y, f2.z, f2.w), f3.w, t1) && r1 != -1 && t1 <= best_key;
-            const bool swap = h1 && (!h0 || t1 < t0);           // the nearer child first
-            const int32_t ra = swap ? r1 : r0, rb = swap ? r0 : r1;
-            const bool ha = swap ? h1 : h0, hb = swap ? h0 : h1;
-            const float tb = swap ? t0 : t1;
-            int next = -1;
-            if (ha) {
-                if (ra < 0) leaf(ra);
-                else next = ra;
-            }
-            if (hb && tb <= best_key) {
-                if (rb < 0) leaf(rb);
-                else if (next < 0) next = rb;
-                else { col[sp * kRenderBlock] = (uint32_t)rb; ++sp; }
-            }
-            if (next < 0) {
-                if (sp == 0) break;
-                --sp;
-                next = (int)col[sp * kRenderBlock];
-            }
-            node = next;
-        }
-    }
-}
-
-// The planes folded as check_hit folds them, after the spheres
-template <typename ScenePtr>
-__device__ __forceinline__ void bvh_fold_planes(ScenePtr S, int ns, int np, V3 o, V3 d, float &best_key, int &best_idx, bool &best_just)
-{
-    if (!best_just) { best_key = __builtin_nanf(""); best_idx = 0; }    // no sphere hit: check_hit's accumulator is still unfilled
-    fold_planes([&](int k) -> float4 { return S[ns + k]; }, ns, np, o, d, best_key, best_idx, best_just);   // check_hit's fold
-}
-
 // THE TRIANGLE TEST (an extension: the reference has no triangle).  A record is (v0, nx) (v1, ny) (v2, nz), n the unit normal the host
 // derived once (ptmi_mesh.cpp).  Every operation is an f32 operation rounded on its own, in this order (tests/cxx/mesh_traverse.c
 // restates it verbatim):
@@ -165,6 +53,16 @@ __device__ PTMI_MESH_EXACT_INLINE HitSel check_hit_mesh_exact(const float4 *by_i
     return best;
 }
 
+// The triangle hierarchy's box test for the ray (o, d): the margin of check_hit_mesh's comment, o1 the L1 norm of the origin
+__device__ __forceinline__ auto mesh_slab(V3 o, V3 d)
+{
+    const BvhRay R = bvh_ray(o, d);
+    const float o1 = (__builtin_fabsf(o.x) + __builtin_fabsf(o.y)) + __builtin_fabsf(o.z);
+    return [=](V3 c, V3 h, float, float &t_near) {
+        return bvh_slab(R, c, h, [=](float p1, float) { return ((p1 + o1) * 0x1p-16f + 0x1p-30f) * (1.0f + 0x1p-10f); }, t_near);
+    };
+}
+
 // check_hit_mesh returns what the fold over spheres ++ planes ++ triangles returns, bit for bit:
 //   * the spheres and the planes as check_hit_bvh finds them (the same walk, the same plane fold, the same stack);
 //   * then the triangle hierarchy, the accumulator carried in: a triangle replaces it where the fold's `<=` fails, or at an equal key
@@ -193,18 +91,12 @@ __device__ __forceinline__ HitSel check_hit_mesh(const MeshView &M, ScenePtr S, 
     bvh_fold_planes(S, ns, np, o, d, best_key, best_idx, best_just);
     if (M.n_kept > 0) {
         const int first_triangle = ns + np;
-        const V3 inv = mk(bvh_inv_of(d.x), bvh_inv_of(d.y), bvh_inv_of(d.z));
-        const V3 ainv = mk(__builtin_fabsf(inv.x), __builtin_fabsf(inv.y), __builtin_fabsf(inv.z));
-        const float o1 = (__builtin_fabsf(o.x) + __builtin_fabsf(o.y)) + __builtin_fabsf(o.z);
         // the bound a child's entry distance is held to: the accumulator's key, or everything while it holds no key (NaN)
         auto bound = [&]() { return best_key == best_key ? best_key : kInfinite; };
-        auto slab = [&](V3 c, V3 h, float &t_near) {
-            PTMI_SLAB_REACH(c, h, o);                        // ex, ey, ez, p1 (p2 is the sphere walk's)
-            (void)p2;
-            const float m = PTMI_MESH_MARGIN(p1, o1);
-            PTMI_SLAB_TEST(h, m, inv, ainv, kBvhFar, t_near);   // t_near, t_far
-            return t_near <= t_far;
-        };
+        // bvh_walk's loop (ptmi_bvh_device.h), written out: through bvh_walk the compiler lays this one search out otherwise, and that
+        // code is not the same speed -- renders up to 18 % faster, closest-hit queries on coherent rays 60 % slower
+        // (profiles/one_walk_ab.txt).  A change to the walk is made in both places.
+        const auto slab = mesh_slab(o, d);
         auto leaf = [&](int32_t ref) {
             const uint32_t v = (uint32_t)(-1 - ref);
             const int first = (int)(v >> 8), count = (int)(v & 255u);
@@ -220,8 +112,8 @@ __device__ __forceinline__ HitSel check_hit_mesh(const MeshView &M, ScenePtr S, 
             const float4 f0 = M.nodes[4 * node], f1 = M.nodes[4 * node + 1], f2 = M.nodes[4 * node + 2], f3 = M.nodes[4 * node + 3];
             const int32_t r0 = (int32_t)f2u(f3.x), r1 = (int32_t)f2u(f3.y);
             float t0, t1;
-            const bool h0 = slab(mk(f0.x, f0.y, f0.z), mk(f1.z, f1.w, f2.x), t0) && r0 != -1 && t0 <= bound();
-            const bool h1 = slab(mk(f0.w, f1.x, f1.y), mk(f2.y, f2.z, f2.w), t1) && r1 != -1 && t1 <= bound();
+            const bool h0 = slab(mk(f0.x, f0.y, f0.z), mk(f1.z, f1.w, f2.x), f3.z, t0) && r0 != -1 && t0 <= bound();
+            const bool h1 = slab(mk(f0.w, f1.x, f1.y), mk(f2.y, f2.z, f2.w), f3.w, t1) && r1 != -1 && t1 <= bound();
             const bool swap = h1 && (!h0 || t1 < t0);           // the nearer child first
             const int32_t ra = swap ? r1 : r0, rb = swap ? r0 : r1;
             const bool ha = swap ? h1 : h0, hb = swap ? h0 : h1;

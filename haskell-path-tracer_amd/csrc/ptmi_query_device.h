@@ -30,11 +30,11 @@ namespace {
 //       - triangles: a NaN t makes the hit point, the three edge functions and their `>= 0` fail: no Just has a NaN key.  (A triangle of
 //         zero area has a NaN normal and is never a Just.)  A Just at t = +inf is not excluded by this argument; it is not a NaN, and the
 //         lane that meets one takes the full search.
-//   * NEVER PRUNE AN OCCLUDER.  The hierarchies are walked by check_hit_bvh's and check_hit_mesh's rule with the bound held at lim: a
-//     child is entered when its widened box (PTMI_SPHERE_MARGIN / PTMI_MESH_MARGIN, PTMI_SLAB_TEST: the same text) is hit at an entry distance
+//   * NEVER PRUNE AN OCCLUDER.  The hierarchies are walked by check_hit_bvh's walk (bvh_walk), whose rule check_hit_mesh's is, with the bound held at
+//     lim: a child is entered when its widened box (bvh_sphere_slab, mesh_slab: their box tests) is hit at an entry distance
 //     t_near <= lim.  Their margins guarantee that a primitive accepted at key t lies under children with t_near <= t; an occluder has
 //     t < lim, so every box above it is entered.  What is pruned holds no occluder; what is skipped by leaving early holds no NaN.
-//   * THE FULL SEARCH is the closest hit itself -- check_hit, check_hit_bvh's parts on this walk's stack (closest_bvh), check_hit_mesh --
+//   * THE FULL SEARCH is the closest hit itself -- check_hit, check_hit_bvh behind its admission test (closest_bvh), check_hit_mesh --
 //     and the compare: for rays the walk does not serve, and for lanes that met a Just key that is not < FLT_MAX.
 //   * THE STACK is check_hit_bvh's column in LDS (bvh_stack_column: one array per kernel, shared with check_hit_mesh and closest_bvh).
 enum : int { kAnyNone = 0, kAnyHit = 1, kAnyFull = 2 };      // no occluder met | an occluder | the lane takes the full search
@@ -80,84 +80,23 @@ __device__ __forceinline__ int any_hit_spheres_linear(ScenePtr S, int ns, V3 o, 
     return found;
 }
 
-// A hierarchy walked with the bound held at lim: check_hit_bvh's loop, leaving at the first leaf that answers.  slab(c, h, inv_2r,
-// t_near) is the box test, leaf(first, count) tests the primitives at positions [first, first + count) of the leaf order.
-template <typename Slab, typename Leaf>
-__device__ __forceinline__ int any_hit_walk(const float4 *nodes, uint32_t *col, float lim, Slab slab, Leaf leaf)
-{
-    auto at_leaf = [&](int32_t ref) {
-        const uint32_t v = (uint32_t)(-1 - ref);
-        return leaf((int)(v >> 8), (int)(v & 255u));
-    };
-    int node = 0, sp = 0;
-    while (true) {
-        const float4 f0 = nodes[4 * node], f1 = nodes[4 * node + 1], f2 = nodes[4 * node + 2], f3 = nodes[4 * node + 3];
-        const int32_t r0 = (int32_t)f2u(f3.x), r1 = (int32_t)f2u(f3.y);
-        float t0, t1;
-        const bool h0 = slab(mk(f0.x, f0.y, f0.z), mk(f1.z, f1.w, f2.x), f3.z, t0) && r0 != -1 && t0 <= lim;
-        const bool h1 = slab(mk(f0.w, f1.x, f1.y), mk(f2.y, f2.z, f2.w), f3.w, t1) && r1 != -1 && t1 <= lim;
-        const bool swap = h1 && (!h0 || t1 < t0);           // the nearer child first: the likelier occluder
-        const int32_t ra = swap ? r1 : r0, rb = swap ? r0 : r1;
-        const bool ha = swap ? h1 : h0, hb = swap ? h0 : h1;
-        int next = -1;
-        if (ha) {
-            if (ra < 0) { const int r = at_leaf(ra); if (r != kAnyNone) return r; }
-            else next = ra;
-        }
-        if (hb) {
-            if (rb < 0) { const int r = at_leaf(rb); if (r != kAnyNone) return r; }
-            else if (next < 0) next = rb;
-            else { col[sp * kRenderBlock] = (uint32_t)rb; ++sp; }
-        }
-        if (next < 0) {
-            if (sp == 0) break;
-            --sp;
-            next = (int)col[sp * kRenderBlock];
-        }
-        node = next;
-    }
-    return kAnyNone;
-}
-
-// The sphere hierarchy: bvh_walk_spheres' box test and leaf test
+// The hierarchies walked with the bound held at lim, leaving at the first primitive that answers
 __device__ __forceinline__ int any_hit_spheres(const BvhView &B, uint32_t *col, V3 o, V3 d, float eta, float lim)
 {
-    const float G = 0x1p-19f + 2.0f * eta, G_lin = G + 0x1p-19f, sqrt_G = __builtin_sqrtf(G);
-    const V3 inv = mk(bvh_inv_of(d.x), bvh_inv_of(d.y), bvh_inv_of(d.z));
-    const V3 ainv = mk(__builtin_fabsf(inv.x), __builtin_fabsf(inv.y), __builtin_fabsf(inv.z));
-    auto slab = [&](V3 c, V3 h, float inv_2r, float &t_near) {
-        PTMI_SLAB_REACH(c, h, o);                            // ex, ey, ez, p1, p2
-        const float m = PTMI_SPHERE_MARGIN(p1, p2, inv_2r);
-        PTMI_SLAB_TEST(h, m, inv, ainv, kBvhFar, t_near);    // t_near, t_far
-        return t_near <= t_far;
-    };
-    auto leaf = [&](int first, int count) {
+    return bvh_walk(B.nodes, col, [=]() { return lim; }, bvh_sphere_slab(o, d, eta), [&](int first, int count) {
         for (int k = 0; k < count; ++k) {
-            const float4 g = B.geom[first + k];
-            PTMI_SPHERE_TEST(g, o, d);                       // tca, x, cand
-            const float t = tca - sqrt_rn(x);
-            const int r = any_hit_key(cand && !(t < 0.0f), t, lim);
+            float t;
+            const bool just = bvh_sphere_just(B.geom[first + k], o, d, t);
+            const int r = any_hit_key(just, t, lim);
             if (r != kAnyNone) return r;
         }
         return (int)kAnyNone;
-    };
-    return any_hit_walk(B.nodes, col, lim, slab, leaf);
+    });
 }
 
-// The triangle hierarchy: check_hit_mesh's box test and leaf test
 __device__ __forceinline__ int any_hit_triangles(const MeshView &M, uint32_t *col, V3 o, V3 d, float lim)
 {
-    const V3 inv = mk(bvh_inv_of(d.x), bvh_inv_of(d.y), bvh_inv_of(d.z));
-    const V3 ainv = mk(__builtin_fabsf(inv.x), __builtin_fabsf(inv.y), __builtin_fabsf(inv.z));
-    const float o1 = (__builtin_fabsf(o.x) + __builtin_fabsf(o.y)) + __builtin_fabsf(o.z);
-    auto slab = [&](V3 c, V3 h, float, float &t_near) {
-        PTMI_SLAB_REACH(c, h, o);                            // ex, ey, ez, p1
-        (void)p2;
-        const float m = PTMI_MESH_MARGIN(p1, o1);
-        PTMI_SLAB_TEST(h, m, inv, ainv, kBvhFar, t_near);    // t_near, t_far
-        return t_near <= t_far;
-    };
-    auto leaf = [&](int first, int count) {
+    return bvh_walk(M.nodes, col, [=]() { return lim; }, mesh_slab(o, d), [&](int first, int count) {
         for (int k = 0; k < count; ++k) {
             const float4 ga = M.geom[3 * (first + k)], gb = M.geom[3 * (first + k) + 1], gc = M.geom[3 * (first + k) + 2];
             PTMI_TRIANGLE_TEST(ga, gb, gc, o, d);            // t, just
@@ -165,23 +104,7 @@ __device__ __forceinline__ int any_hit_triangles(const MeshView &M, uint32_t *co
             if (r != kAnyNone) return r;
         }
         return (int)kAnyNone;
-    };
-    return any_hit_walk(M.nodes, col, lim, slab, leaf);
-}
-
-// check_hit_bvh behind its test of what the hierarchy serves, from its parts (ptmi_mesh_device.h) on the caller's stack: the full
-// search of a BVH scene's lane that met a plane key it cannot rank
-template <typename ScenePtr>
-__device__ __forceinline__ HitSel closest_bvh(const BvhView &B, uint32_t *col, ScenePtr S, int ns, int np, V3 o, V3 d, float eta)
-{
-    float best_key = kInfinite;
-    int best_idx = 0x7fffffff;
-    bool best_just = false;
-    if (ns > 0) bvh_walk_spheres(B, col, o, d, eta, best_key, best_idx, best_just);
-    bvh_fold_planes(S, ns, np, o, d, best_key, best_idx, best_just);
-    if (best_just && !(best_key < kInfinite)) return check_hit_exact(S, ns, np, o, d);
-    HitSel best; best.t = best_key; best.idx = best_idx; best.just = best_just;
-    return best;
+    });
 }
 
 __device__ __forceinline__ bool occluded_by(HitSel h, float t_max) { return h.just && h.t < t_max; }

@@ -2,7 +2,7 @@
 render loops with the mesh checkHit (tests/cxx/mesh_reference.c: the literal fold over spheres ++ planes ++ triangles, a triangle's hit
 record from its unit normal and its own material).  Bit for bit on all seven planes: Inline at two bounce limits, the Streams chain under
 both seed rules, the GLASS tree walk with glass triangles, ragged image sizes, render1 / render1_chained, and a partitioned context whose
-stitched parts equal the whole.  Also: with no triangles, check_hit_mesh's copy of the sphere walk and plane fold answers exactly as
+stitched parts equal the whole.  Also: with no triangles, check_hit_mesh's sphere walk and plane fold answer exactly as
 check_hit_bvh does."""
 import os
 import sys
@@ -131,8 +131,8 @@ def test_partitioned_context_stitches_the_mesh_reference(pkg, ora, ref):
 
 
 def test_without_triangles_check_hit_mesh_answers_as_check_hit_bvh(ctx):
-    """check_hit_mesh carries its own copy of check_hit_bvh's sphere walk and plane fold (so that the BVH kernels keep their code):
-    the two must stay the same, bit for bit, on the BVH tests' adversarial rays."""
+    """check_hit_mesh runs check_hit_bvh's sphere walk and plane fold before its triangles, behind an admission test of its own:
+    the two must answer the same, bit for bit, on the BVH tests' adversarial rays."""
     spheres, planes = bvh_rays.adversarial_scene(20000, seed=51)
     rays = bvh_rays.adversarial_rays(spheres, 100_000, seed=51)
     ctx.set_scene_bvh(spheres, planes)
