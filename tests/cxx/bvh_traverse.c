@@ -3,13 +3,15 @@
  * (csrc/ptmi_bvh_device.h) does -- the same admission of a ray, the same per-ray margin, the same slab test, the same pruning against
  * the best key -- so that tests/test_bvh_traversal.py can show, without a GPU, that the padding and the pruning never lose the hit
  * the linear fold (ora_check_hit) finds.  Built by that test with the oracle's flags (no contraction, no fast-math).
- * Also the linear fold itself with the index kept (ora_check_hit returns the hit record only). */
+ * Also the linear fold itself with the index kept (ora_check_hit returns the hit record only).  The box test is traverse_slabs.h's, which
+ * any_hit_traverse.c (the occlusion walks) shares. */
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "../../oracle/pt_oracle.h"
 #include "../../include/ptmi.h"
+#include "traverse_slabs.h"
 
 #define INF_KEY 3.40282346638528859812e+38f    /* kInfinite: maybe infinite fst (Trace.hs:450-451) */
 
@@ -46,12 +48,6 @@ void lin_check_hit(const ora_sphere *s, int ns, const ora_plane *p, int np, cons
     }
 }
 
-static float inv_of(float v)
-{
-    const float c = fabsf(v) < 0x1p-80f ? copysignf(0x1p-80f, v) : v;
-    return 1.0f / c;
-}
-
 static sel bvh_one(const ptmi_bvh_node *nodes, const int32_t *order, const float lo[3], const float hi[3],
                    const ora_sphere *s, int ns, const ora_plane *p, int np, ora_ray r, int64_t *tests)
 {
@@ -72,7 +68,6 @@ static sel bvh_one(const ptmi_bvh_node *nodes, const int32_t *order, const float
     if (ns > 0) {
         const float G = 0x1p-19f + 2.0f * eta, G_lin = G + 0x1p-19f, sqrt_G = sqrtf(G);
         const float inv[3] = {inv_of(d[0]), inv_of(d[1]), inv_of(d[2])};
-        const float kFar = 1.0f + 2.0f * (3.0f * 0x1p-24f) / (1.0f - 3.0f * 0x1p-24f);
         int stack[PTMI_BVH_MAX_DEPTH];
         int node = 0, sp = 0;
         for (;;) {
@@ -80,19 +75,10 @@ static sel bvh_one(const ptmi_bvh_node *nodes, const int32_t *order, const float
             float tn[2];
             int h[2];
             for (int c = 0; c < 2; ++c) {
-                float e[3], ab[3];
-                for (int a = 0; a < 3; ++a) { e[a] = nd->center[c][a] - o[a]; ab[a] = fabsf(e[a]) + nd->half[c][a]; }
-                const float p1 = (ab[0] + ab[1]) + ab[2], p2 = (ab[0] * ab[0] + ab[1] * ab[1]) + ab[2] * ab[2];
-                const float m = ((fminf(sqrt_G * p1, (G * p2) * nd->inv_2r[c]) + G_lin * p1) + 0x1p-30f) * (1.0f + 0x1p-10f);
-                float t_near = 0.0f, t_far = INFINITY, tlo[3], thi[3];
-                for (int a = 0; a < 3; ++a) {
-                    const float tm = e[a] * inv[a], hh = (nd->half[c][a] + m) * fabsf(inv[a]);
-                    tlo[a] = tm - hh; thi[a] = tm + hh;
-                }
-                t_near = fmaxf(fmaxf(tlo[0], tlo[1]), fmaxf(tlo[2], 0.0f));
-                t_far = fminf(fminf(thi[0], thi[1]), thi[2]) * kFar;
+                float t_near;
+                const int in_box = sphere_child_slab(nd, c, o, inv, G, G_lin, sqrt_G, 1.0f, &t_near);      /* traverse_slabs.h */
                 tn[c] = t_near;
-                h[c] = t_near <= t_far && nd->ref[c] != -1 && t_near <= best_key;
+                h[c] = in_box && nd->ref[c] != -1 && t_near <= best_key;
             }
             const int sw = h[1] && (!h[0] || tn[1] < tn[0]);
             const int ra = sw ? nd->ref[1] : nd->ref[0], rb = sw ? nd->ref[0] : nd->ref[1];

@@ -4,7 +4,8 @@
  *   mesh_walk_check_hit: the spheres and planes by the same fold, then the triangle hierarchy ptmi_mesh_layout exports, walked as
  *     check_hit_mesh (csrc/ptmi_mesh_device.h) walks it -- the same admission of a ray, margin, slab test, pruning against the best key
  *     and tie rule -- so that tests can show that the padding and the pruning never lose the hit the linear fold finds.
- * Built with the oracle's flags (no contraction, no fast-math).
+ * Built with the oracle's flags (no contraction, no fast-math).  The box test is traverse_slabs.h's and the triangle test triangle_test.h's;
+ * any_hit_traverse.c (the occlusion walks) shares both.
  *
  * The triangle test, verbatim from ptmi_mesh_device.h (every operation an f32 operation rounded on its own):
  *   n = cross(v1 - v0, v2 - v0) (linear's component order), nn = dot(n, n); zero area iff !(nn > 0) -- never hit; else
@@ -20,19 +21,12 @@
 
 #include "../../oracle/pt_oracle.h"
 #include "../../include/ptmi.h"
+#include "traverse_slabs.h"
+#include "triangle_test.h"
 
 #define INF_KEY 3.40282346638528859812e+38f
 
-typedef struct { float x, y, z; } v3;
 typedef struct { float t; int idx; int just; } sel;
-
-static v3 mk(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-static v3 sub(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-static float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-static v3 cross(v3 a, v3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-
-/* the record the host stores: vertices and the unit normal (NaN for zero area) */
-typedef struct { v3 v0, v1, v2, n; } trec;
 
 static trec record_of(const ptmi_triangle *t)
 {
@@ -44,18 +38,6 @@ static trec record_of(const ptmi_triangle *t)
     const float len = sqrtf(nn);
     r.n = mk(n.x / len, n.y / len, n.z / len);
     return r;
-}
-
-static int tri_test(const trec *r, v3 o, v3 d, float *t_out)
-{
-    const float denom = dot(d, r->n);
-    const float t = dot(sub(r->v0, o), r->n) / denom;
-    const v3 p = mk(o.x + d.x * t, o.y + d.y * t, o.z + d.z * t);
-    const float w0 = dot(cross(sub(r->v1, r->v0), sub(p, r->v0)), r->n);
-    const float w1 = dot(cross(sub(r->v2, r->v1), sub(p, r->v1)), r->n);
-    const float w2 = dot(cross(sub(r->v0, r->v2), sub(p, r->v2)), r->n);
-    *t_out = t;
-    return !(denom > 1e-6f) && !(t < 0.0f) && w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f && !isnan(r->n.x);
 }
 
 static ora_ray ray_of(const float *q)
@@ -111,12 +93,6 @@ void mesh_lin_check_hit(const ora_sphere *s, int ns, const ora_plane *p, int np,
     }
 }
 
-static float inv_of(float v)
-{
-    const float c = fabsf(v) < 0x1p-80f ? copysignf(0x1p-80f, v) : v;
-    return 1.0f / c;
-}
-
 /* check_hit_mesh with the spheres and planes by the fold: returns the triangles tested (-1 if the ray is not served) */
 static int64_t walk_one(const ptmi_bvh_node *nodes, const int32_t *order, int n_kept, const float lo[3], const float hi[3],
                         const ora_sphere *s, int ns, const ora_plane *p, int np, const trec *tr, int nt, ora_ray r, sel *out)
@@ -149,24 +125,16 @@ static int64_t walk_one(const ptmi_bvh_node *nodes, const int32_t *order, int n_
         const v3 inv = mk(inv_of(d.x), inv_of(d.y), inv_of(d.z));
         const v3 ainv = mk(fabsf(inv.x), fabsf(inv.y), fabsf(inv.z));
         const float o1 = (fabsf(o.x) + fabsf(o.y)) + fabsf(o.z);
-        const float kFar = 1.0f + 2.0f * (3.0f * 0x1p-24f) / (1.0f - 3.0f * 0x1p-24f);
+        const float inv3[3] = {inv.x, inv.y, inv.z}, ainv3[3] = {ainv.x, ainv.y, ainv.z};
         int stack[PTMI_BVH_MAX_DEPTH + 1], sp = 0, node = 0;
         for (;;) {
             const ptmi_bvh_node *nd = &nodes[node];
             float tn[2];
             int h[2];
             for (int c = 0; c < 2; ++c) {
-                const float ex = nd->center[c][0] - o.x, ey = nd->center[c][1] - o.y, ez = nd->center[c][2] - o.z;
-                const float ax = fabsf(ex) + nd->half[c][0], ay = fabsf(ey) + nd->half[c][1], az = fabsf(ez) + nd->half[c][2];
-                const float p1 = (ax + ay) + az;
-                const float m = ((p1 + o1) * 0x1p-16f + 0x1p-30f) * (1.0f + 0x1p-10f);
-                const float tmx = ex * inv.x, hx = (nd->half[c][0] + m) * ainv.x;
-                const float tmy = ey * inv.y, hy = (nd->half[c][1] + m) * ainv.y;
-                const float tmz = ez * inv.z, hz = (nd->half[c][2] + m) * ainv.z;
-                tn[c] = fmaxf(fmaxf(tmx - hx, tmy - hy), fmaxf(tmz - hz, 0.0f));
-                const float tf = fminf(fminf(tmx + hx, tmy + hy), tmz + hz) * kFar;
+                const int in_box = mesh_child_slab(nd, c, o3, inv3, ainv3, o1, 1.0f, &tn[c]);      /* traverse_slabs.h */
                 const float bound = best_key == best_key ? best_key : INF_KEY;
-                h[c] = tn[c] <= tf && nd->ref[c] != -1 && tn[c] <= bound;
+                h[c] = in_box && nd->ref[c] != -1 && tn[c] <= bound;
             }
             const int swap = h[1] && (!h[0] || tn[1] < tn[0]);
             const int32_t ra = swap ? nd->ref[1] : nd->ref[0], rb = swap ? nd->ref[0] : nd->ref[1];

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(HERE)
 for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
+from t_max_families import T_MAX_OF_HITS, T_MAX_OF_MISSES, t_max_for  # noqa: E402
 
 CASES = ["1 closest hit", "2 sizes alignment guards", "3 hit record", "4 occluded", "5 caller stream", "6 after device updates", "7 refusals",
          "8 render after queries", "9 non-finite scene data"]
@@ -26,8 +27,6 @@ N_RAYS = 4096
 SIZES = (0, 1, 63, 64, 65, 257, N_RAYS)
 GUARD = 64                                            # words on either side of every output
 SENTINEL = 0x7FC0DEAD
-T_MAX_OF_HITS = ("below", "equal", "above", "half", "double", "zero", "minus one", "inf", "nan")
-T_MAX_OF_MISSES = ("one", "inf", "nan")
 
 torch = pkg = B = W = ora = None
 bvh_rays = mesh_rays = None
@@ -159,25 +158,6 @@ class Scene:
             c.set_scene_bvh(self.spheres, self.planes)
         else:
             c.set_scene(self.spheres, self.planes)
-
-
-def t_max_for(sc):
-    """Every family of t_max, dealt round-robin among the hits and among the misses -> (t_max, the specification's answer, family of every ray)"""
-    t, hit = sc.t, sc.idx >= 0
-    t_max = np.zeros(N_RAYS, np.float32)
-    family = np.empty(N_RAYS, object)
-    inf, zero = np.float32(np.inf), np.float32(0.0)
-    of_hit = {"below": np.nextafter(t, zero), "equal": t, "above": np.nextafter(t, inf), "half": np.float32(0.5) * t, "double": np.float32(2.0) * t,
-              "zero": np.zeros_like(t), "minus one": np.full_like(t, -1.0), "inf": np.full_like(t, np.inf), "nan": np.full_like(t, np.nan)}
-    of_miss = {"one": np.ones_like(t), "inf": np.full_like(t, np.inf), "nan": np.full_like(t, np.nan)}
-    for rows, table, names in ((np.flatnonzero(hit), of_hit, T_MAX_OF_HITS), (np.flatnonzero(~hit), of_miss, T_MAX_OF_MISSES)):
-        for k, name in enumerate(names):
-            mine = rows[k::len(names)]
-            t_max[mine] = table[name][mine]
-            family[mine] = name
-    with np.errstate(invalid="ignore"):
-        want = (hit & (t < t_max)).astype(np.int32)                      # one f32 compare against the closest hit
-    return t_max, want, family
 
 
 # ---- the cases ---------------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,10 @@ The cases are those of the driver's docstrings:
   6 after update_spheres / set_mesh_triangles from device tensors, against a context set afresh
   7 the refusals, through the raw library handle; nothing written
   8 a render between queries equals a render without them on all seven planes
-  9 scene data that is not finite (a linear scene's spheres, a linear and a BVH scene's planes): the full search, the specification's answers"""
+  9 scene data that is not finite (a linear scene's spheres, a linear and a BVH scene's planes): the full search, the specification's answers
+The families of t_max are tests/t_max_families.py's.  Occlusion beyond these five scenes -- other trees (refitted, device-built), scales,
+offsets, the admission brackets and the guards -- is held to the closest hit by tests/test_any_hit_traversal.py (a CPU restatement of the
+any-hit walks, tests/cxx/any_hit_traverse.c) and tests/test_gpu_any_hit.py (tests/any_hit_driver.py, on the device)."""
 import os
 import subprocess
 import sys
