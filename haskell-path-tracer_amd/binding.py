@@ -25,6 +25,8 @@ FORM_AUTO, FORM_STREAM, FORM_PIXEL = 0, 1, 2
 PTMI_OK, PTMI_EINVAL, PTMI_ENODEVICE, PTMI_EHIP, PTMI_ENOMEM, PTMI_ESTATE, PTMI_ELIMIT, PTMI_ESTALE = 0, -1, -2, -3, -4, -5, -6, -7
 MAX_PRIMITIVES, MAX_BVH_SPHERES, MAX_BVH_PLANES, BVH_MAX_DEPTH, BVH_LEAF_MAX = 1024, 1 << 22, 64, 24, 4
 MAX_MESH_TRIANGLES = 1 << 22
+RAY_ORDER_MAX = 1 << 22
+RAY_KEY_NOT_PLACED = 1 << 44                                     # ptmi_ray_order_keys: a ray with a non-finite word or a zero direction
 # ptmi_bvh_node: the boxes of both children (centre, half extent), the child references, 1 / (2 r_min) per child
 BVH_NODE_DTYPE = np.dtype([("center", "<f4", (2, 3)), ("half", "<f4", (2, 3)), ("ref", "<i4", 2), ("inv_2r", "<f4", 2)])
 
@@ -136,6 +138,12 @@ SYMBOLS = {
     "ptmi_eval_check_hit": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_trace_rays_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_occluded_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "ptmi_ray_order_bytes": (C.c_size_t, [C.c_int]),
+    "ptmi_ray_order_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t]),
+    "ptmi_ray_order": (C.c_int, [_vp, C.c_int, _vp]),
+    "ptmi_ray_order_keys": (C.c_int, [_vp, C.c_int, _vp]),
+    "ptmi_trace_rays_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_occluded_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
@@ -249,6 +257,41 @@ def bvh_refit_layout(spheres, nodes, order):
     if rc != PTMI_OK:
         raise PtmiError(rc, "ptmi_bvh_refit_layout")
     return out
+
+
+def _host_rays(rays):
+    """(n, 6) float32 host rays -> a contiguous array"""
+    r = np.asarray(rays)
+    if r.dtype != np.float32 or r.ndim != 2 or r.shape[1] != 6 or not r.flags.c_contiguous:
+        raise ValueError("rays must be a contiguous float32 array of shape (n, 6), not %s %r" % (r.dtype, r.shape))
+    return r
+
+
+def ray_order_keys(rays):
+    """ptmi_ray_order_keys: the key every ray of the batch is ordered by (host code, no device; csrc/ptmi_ray_order.h states it) -> uint64
+    (n,), RAY_KEY_NOT_PLACED for a ray with a non-finite word or a zero direction."""
+    r = _host_rays(rays)
+    keys = np.zeros(r.shape[0], np.uint64)
+    rc = load_library().ptmi_ray_order_keys(_ptr(r) if r.size else None, r.shape[0], _ptr(keys) if r.size else None)
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_ray_order_keys")
+    return keys
+
+
+def ray_order(rays):
+    """ptmi_ray_order: the order ptmi_ray_order_device gives the batch (host code, no device) -> int32 (n,): the ray of every position,
+    ascending by (key, index)."""
+    r = _host_rays(rays)
+    order = np.zeros(r.shape[0], np.int32)
+    rc = load_library().ptmi_ray_order(_ptr(r) if r.size else None, r.shape[0], _ptr(order) if r.size else None)
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_ray_order")
+    return order
+
+
+def ray_order_bytes(n):
+    """ptmi_ray_order_bytes: the workspace ptmi_ray_order_device needs for n rays."""
+    return int(load_library().ptmi_ray_order_bytes(int(n)))
 
 
 def _device_rows(t, words, what):
@@ -706,7 +749,7 @@ class Context:
         return t, idx, just
 
     # -- ray queries on the device ------------------------------------------------------
-    def trace_rays(self, rays, hit=False, out=None):
+    def trace_rays(self, rays, hit=False, out=None, index=None):
         """ptmi_trace_rays_device: the closest hit of every ray against the current scene, on the context's stream, nothing leaving the
         device.  rays: a contiguous float32 device tensor of shape (n, 6) -- origin, direction -- anything with is_cuda and data_ptr();
         the caller orders its writes before the context's stream and keeps the tensors until the stream has passed the call (after
@@ -714,37 +757,79 @@ class Context:
         synchronize() before the results are read).
         -> (t, idx), or (t, idx, hit) with hit=True: t float32 (n,), idx int32 (n,) -- spheres, then planes, then triangles; a miss is
         t 0, idx -1 -- and hit float32 (n, 6), position and normal, zeros for a miss.  They are allocated with torch.empty on the rays'
-        device unless out=(t, idx) or out=(t, idx, hit) gives the caller's own."""
+        device unless out=(t, idx) or out=(t, idx, hit) gives the caller's own.
+        index: an int32 device tensor (m,) -- ptmi_trace_rays_indexed_device: only the rays it names are traced, in its order (ray_order's,
+        or a caller's list of live rays), each answer at its ray's position; an entry outside [0, n) is skipped.  Outputs allocated here
+        are then filled with the miss record first (t 0, idx -1, zeros), so the positions no entry names are defined -- by torch, on its
+        current stream: the context must launch on that stream (set_stream), as for any input torch writes.  A caller's out= is left as
+        it is at those positions."""
         d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
         n = int(rays.shape[0])
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
         if out is not None:
             if len(out) not in (2, 3):
                 raise ValueError("out must be (t, idx) or (t, idx, hit)")
             hit = len(out) == 3
             outs = tuple(out)
-        else:
+        elif index is None:
             import torch
             outs = (torch.empty(n, dtype=torch.float32, device=rays.device), torch.empty(n, dtype=torch.int32, device=rays.device))
             if hit:
                 outs += (torch.empty((n, 6), dtype=torch.float32, device=rays.device),)
+        else:
+            import torch
+            outs = (torch.zeros(n, dtype=torch.float32, device=rays.device), torch.full((n,), -1, dtype=torch.int32, device=rays.device))
+            if hit:
+                outs += (torch.zeros((n, 6), dtype=torch.float32, device=rays.device),)
         d_t = _device_tensor(outs[0], "float32", (n,), "t")
         d_idx = _device_tensor(outs[1], "int32", (n,), "idx")
         d_hit = _device_tensor(outs[2], "float32", (n, 6), "hit") if hit else None
-        self._check(self._lib.ptmi_trace_rays_device(self._h, d_rays, n, d_t, d_idx, d_hit))
+        if index is None:
+            self._check(self._lib.ptmi_trace_rays_device(self._h, d_rays, n, d_t, d_idx, d_hit))
+        else:
+            self._check(self._lib.ptmi_trace_rays_indexed_device(self._h, d_rays, n, d_index, int(index.shape[0]), d_t, d_idx, d_hit))
         return outs
 
-    def occluded(self, rays, t_max, out=None):
+    def occluded(self, rays, t_max, out=None, index=None):
         """ptmi_occluded_device: 1 where the closest hit of a ray is nearer than its t_max, else 0 (a NaN or non-positive t_max: 0), found
         by an any-hit walk on the context's stream.  rays as trace_rays takes them, t_max a contiguous float32 device tensor of shape
-        (n,) -> an int32 device tensor (n,): `out`, or one allocated with torch.empty on the rays' device."""
+        (n,) -> an int32 device tensor (n,): `out`, or one allocated with torch.empty on the rays' device.
+        index: as for trace_rays (ptmi_occluded_indexed_device); an output allocated here is then filled with 0 first."""
         d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
         n = int(rays.shape[0])
         d_t_max = _device_tensor(t_max, "float32", (n,), "t_max")
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
         if out is None:
             import torch
-            out = torch.empty(n, dtype=torch.int32, device=rays.device)
+            out = (torch.empty if index is None else torch.zeros)(n, dtype=torch.int32, device=rays.device)
         d_out = _device_tensor(out, "int32", (n,), "out")
-        self._check(self._lib.ptmi_occluded_device(self._h, d_rays, d_t_max, n, d_out))
+        if index is None:
+            self._check(self._lib.ptmi_occluded_device(self._h, d_rays, d_t_max, n, d_out))
+        else:
+            self._check(self._lib.ptmi_occluded_indexed_device(self._h, d_rays, d_t_max, n, d_index, int(index.shape[0]), d_out))
+        return out
+
+    def ray_order(self, rays, out=None, work=None):
+        """ptmi_ray_order_device: a coherent order for the batch, on the context's stream, nothing leaving the device -> an int32 device
+        tensor (n,): the ray of every position, ascending by (key, index) -- the index= of trace_rays / occluded.  No scene is needed.
+        out: the caller's own int32 (n,); work: a uint8 device tensor of at least ray_order_bytes(n) elements, 8-byte aligned, scratch
+        while the call is in flight.  Both are allocated with torch.empty on the rays' device by default; a workspace allocated here
+        goes back to torch's allocator when this returns, which is safe when the context launches on torch's current stream
+        (set_stream) -- otherwise give work= and keep it until the stream has passed the call."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        need = int(self._lib.ptmi_ray_order_bytes(n))
+        if out is None or work is None:
+            import torch
+            if out is None:
+                out = torch.empty(n, dtype=torch.int32, device=rays.device)
+            if work is None:
+                work = torch.empty(need, dtype=torch.uint8, device=rays.device)
+        d_out = _device_tensor(out, "int32", (n,), "out")
+        d_work = _device_tensor(work, "uint8", (None,), "work")
+        if int(work.shape[0]) < need:
+            raise ValueError("work must hold ray_order_bytes(n) = %d bytes, not %d" % (need, int(work.shape[0])))
+        self._check(self._lib.ptmi_ray_order_device(self._h, d_rays, n, d_out, d_work, int(work.shape[0])))
         return out
 
     def eval_sincos(self, x):

@@ -972,6 +972,35 @@ int ptmi_occluded_device(ptmi_ctx *c, const float *d_rays, const float *d_t_max,
     return PTMI_OK;
 }
 
+// ... and through an index: the plain entries' refusals, then the index's
+int ptmi_trace_rays_indexed_device(ptmi_ctx *c, const float *d_rays, int n, const int32_t *d_index, int m, float *d_t, int32_t *d_idx, float *d_hit)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!d_rays || !d_t || !d_idx)) || m < 0 || (m > 0 && !d_index)) return fail(c, PTMI_EINVAL, "bad ray-query arguments");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (n == 0 || m == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const SceneState &s = c->scene;
+    PTMI_HIP(c, launch_trace_rays_indexed(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
+                                          d_index, m, d_t, d_idx, d_hit, c->stream));
+    return PTMI_OK;
+}
+
+int ptmi_occluded_indexed_device(ptmi_ctx *c, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m, int32_t *d_occluded)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!d_rays || !d_t_max || !d_occluded)) || m < 0 || (m > 0 && !d_index)) return fail(c, PTMI_EINVAL, "bad ray-query arguments");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (n == 0 || m == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const SceneState &s = c->scene;
+    PTMI_HIP(c, launch_occluded_indexed(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, s.sphere_reach,
+                                        d_rays, d_t_max, n, d_index, m, d_occluded, c->stream));
+    return PTMI_OK;
+}
+
 int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *cos_out)
 {
     if (!c) return PTMI_EINVAL;

@@ -269,6 +269,16 @@ hipError_t launch_trace_rays(SceneView scene, const BvhView *bvh, const MeshView
                              hipStream_t stream);
 hipError_t launch_occluded(SceneView scene, const BvhView *bvh, const MeshView *mesh, float reach, const float *rays, const float *t_max, int n,
                            int32_t *occluded, hipStream_t stream);
+// ... and through an index (ptmi_trace_rays_indexed_device, ptmi_occluded_indexed_device; ptmi_query_indexed.hip): entry k < m names ray
+// index[k], answered into position index[k] of the n-sized outputs; an entry outside [0, n) is skipped.
+hipError_t launch_trace_rays_indexed(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, int n, const int32_t *index, int m,
+                                     float *t, int32_t *idx, float *hit, hipStream_t stream);
+hipError_t launch_occluded_indexed(SceneView scene, const BvhView *bvh, const MeshView *mesh, float reach, const float *rays, const float *t_max, int n,
+                                   const int32_t *index, int m, int32_t *occluded, hipStream_t stream);
+// A coherent order for n rays (ptmi_ray_order_device; ptmi_ray_order.hip): order[position] = ray, ascending by (ptmi_ray_order.h's key,
+// index).  work: ray_order_bytes(n) bytes, 8-byte aligned -- the sort's scratch and the box words behind it.
+size_t ray_order_bytes(int n);
+hipError_t launch_ray_order(const float *rays, int n, void *work, int32_t *order, hipStream_t stream);
 // Moving a mesh scene's vertices (ptmi_update_mesh_vertices; ptmi_mesh_refit.hip).  vertices: 9 floats per triangle by original index, device
 // memory; leaf_pos: per triangle its position in the leaf order or -1; result: kRefitWords words (ptmi_mesh_box.h), all ones in
 // [0, kRefitHi), zero behind, at launch.  check writes `result` only; records writes both copies of the records; level the boxes of

@@ -29,6 +29,7 @@
 #ifndef PTMI_H
 #define PTMI_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -753,6 +754,41 @@ int ptmi_partition_global_row(int height, int stripe_rows, int n_parts, int part
  *     (ptmi_group_member) with rays on its device. */
 int ptmi_trace_rays_device(ptmi_ctx *ctx, const float *d_rays, int n, float *d_t, int32_t *d_idx, float *d_hit /* [n][6] position, normal; may be NULL */);
 int ptmi_occluded_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, int32_t *d_occluded);
+
+/* ---- ray order and ray queries through an index ------------------------------- */
+/* The queries above take one lane per ray in the caller's order: a wave whose 64 rays point everywhere walks 64 paths through a hierarchy.
+ * Two things serve the batches real callers send (bounce rays, shadow rays from scattered points, sensor beams), through one mechanism,
+ * an index array of int32 in device memory.  The order and lifetime rules are those of the section above, for every array here, the
+ * workspace included.
+ *   - ptmi_ray_order_device: d_order receives a permutation of 0 .. n - 1, ascending by (key, original index).  The key is a function of
+ *     the rays alone (csrc/ptmi_ray_order.h states it): 24 bits of Morton code of the origin's cell in the box of the batch's origins, then
+ *     20 bits of Morton code of the direction's cell on the octahedral map -- origins major, so bounce rays group by place and a camera's
+ *     rays by direction; a ray with a non-finite word or a zero direction sorts behind every other, in index order.  No scene is needed
+ *     (no PTMI_ESTATE).  d_work: ptmi_ray_order_bytes(n) bytes, 8-byte aligned, scratch while the call is in flight.  Everything is
+ *     enqueued on the context's stream: no host synchronisation, no allocation, no copy to the host.  Refusals enqueue and write nothing:
+ *     PTMI_EINVAL for a negative n, for a NULL pointer with n > 0, for a d_work that is not 8-byte aligned and for work_bytes below
+ *     ptmi_ray_order_bytes(n); PTMI_ELIMIT for n > PTMI_RAY_ORDER_MAX.  n == 0 is PTMI_OK and touches nothing.
+ *   - ptmi_ray_order / ptmi_ray_order_keys: the same order, and the keys themselves (1 << 44 for a ray that is not placed), from HOST rays
+ *     on the host: no context, no device.  The specification the device order is tested against.
+ *   - ptmi_trace_rays_indexed_device / ptmi_occluded_indexed_device: lane k < m takes i = d_index[k]; if 0 <= i < n it answers ray i and
+ *     writes the answer at position i of the outputs -- the n-sized arrays of the plain entries -- with the plain entries' words, bit for
+ *     bit (the same device functions), whatever the index holds.  An entry outside [0, n) is skipped: nothing is read or written for it.
+ *     A position no entry names is left untouched; one named twice is written twice with the same words.  With ptmi_ray_order_device's
+ *     order as the index this is the reordered query; with a caller's list of live rays (m < n), the active-list query.  Refusals are
+ *     the plain entries', and PTMI_EINVAL for a negative m or a NULL d_index with m > 0; m == 0 is PTMI_OK and touches nothing.
+ *   - Ordering pays where rays diverge in a hierarchy (BVH and mesh scenes, incoherent batches) and one order serves several queries; it
+ *     does not pay on a linear scene, which has no hierarchy to diverge in, on rays that are coherent already, or for a single query: the
+ *     order costs about as much as a trace (DESIGN.md 5.9 has the measurements).
+ *   - There is no group form, as above. */
+#define PTMI_RAY_ORDER_MAX (1 << 22)   /* what the builders' sort is tested at */
+size_t ptmi_ray_order_bytes(int n);    /* workspace for n rays; 0 for n <= 0 */
+int ptmi_ray_order_device(ptmi_ctx *ctx, const float *d_rays, int n, int32_t *d_order, void *d_work, size_t work_bytes);
+int ptmi_ray_order(const float *rays, int n, int32_t *order);
+int ptmi_ray_order_keys(const float *rays, int n, uint64_t *keys);
+int ptmi_trace_rays_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, const int32_t *d_index, int m,
+                                   float *d_t, int32_t *d_idx, float *d_hit /* may be NULL */);
+int ptmi_occluded_indexed_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m,
+                                 int32_t *d_occluded);
 
 /* ---- point queries (the reference's unit-test surface) ------------------------ */
 /* Evaluates distanceTo / hit (src/Scene/Intersection.hs:16-64) on the DEVICE for n independent
