@@ -144,6 +144,9 @@ SYMBOLS = {
     "ptmi_ray_order_keys": (C.c_int, [_vp, C.c_int, _vp]),
     "ptmi_trace_rays_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_occluded_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_path_seeds_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "ptmi_trace_paths_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ptmi_trace_paths_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
@@ -831,6 +834,50 @@ class Context:
             raise ValueError("work must hold ray_order_bytes(n) = %d bytes, not %d" % (need, int(work.shape[0])))
         self._check(self._lib.ptmi_ray_order_device(self._h, d_rays, n, d_out, d_work, int(work.shape[0])))
         return out
+
+    # -- paths along a caller's rays ------------------------------------------------------
+    @staticmethod
+    def _seed_tensor(t, n, what):
+        """seeds: a contiguous device tensor (n, 4) of any 4-byte integer dtype -> its pointer"""
+        name = str(getattr(t, "dtype", "")).split(".")[-1]
+        return _device_tensor(t, name if name in ("int32", "uint32") else "int32", (n, 4), what)
+
+    def path_seeds(self, seed0, n, first_index=0, out=None):
+        """ptmi_path_seeds_device: the SFC32 states init_output(seed0) gives pixels first_index .. first_index + n - 1 of an unpartitioned
+        image, on the context's stream -> a device tensor (n, 4): a, b, c, counter per ray -- `out` (any 4-byte integer dtype), or an int32
+        one allocated with torch.empty on torch's current device.  No scene is needed."""
+        n = int(n)
+        if n < 0 or int(first_index) < 0:
+            raise ValueError("n and first_index must not be negative")
+        if out is None:
+            import torch
+            out = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+        d_out = self._seed_tensor(out, n, "out")
+        self._check(self._lib.ptmi_path_seeds_device(self._h, int(seed0) & (2 ** 64 - 1), int(first_index), n, d_out))
+        return out
+
+    def trace_paths(self, rays, seeds, bounce_limit, spp=1, color=None, index=None):
+        """ptmi_trace_paths_device: render Inline along the caller's rays, on the context's stream, nothing leaving the device -- for ray i,
+        spp times: (new, seed') = traceInline bounce_limit scene ray_i seed_i; color_i = new + color_i; seed_i = seed'.  rays as trace_rays
+        takes them (a direction of any length); seeds: a contiguous device tensor (n, 4) of any 4-byte integer dtype (path_seeds makes
+        one), advanced in place; color: a contiguous float32 device tensor (n, 3), accumulated into -- allocated with torch.zeros on the rays'
+        device when not given (by torch, on its current stream: the context must then launch on that stream, set_stream).  -> color.
+        index: an int32 device tensor (m,) -- ptmi_trace_paths_indexed_device: only the rays it names are traced, in its order; an entry
+        outside [0, n) is skipped, a ray no entry names keeps its colour and seed.  It must name a ray at most once: colour and seed are
+        read and written, a ray named twice is a race."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        d_seed = self._seed_tensor(seeds, n, "seeds")
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        if color is None:
+            import torch
+            color = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        d_color = _device_tensor(color, "float32", (n, 3), "color")
+        if index is None:
+            self._check(self._lib.ptmi_trace_paths_device(self._h, d_rays, n, int(bounce_limit), int(spp), d_color, d_seed))
+        else:
+            self._check(self._lib.ptmi_trace_paths_indexed_device(self._h, d_rays, n, d_index, int(index.shape[0]), int(bounce_limit), int(spp), d_color, d_seed))
+        return color
 
     def eval_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

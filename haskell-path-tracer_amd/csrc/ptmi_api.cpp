@@ -1001,6 +1001,46 @@ int ptmi_occluded_indexed_device(ptmi_ctx *c, const float *d_rays, const float *
     return PTMI_OK;
 }
 
+// Paths along the caller's rays: the ray queries' refusals and render Inline's (a GLASS material), then one launch.  The context's state
+// planes, partition, camera and statistics are not touched.
+static int trace_paths(ptmi_ctx *c, const float *d_rays, int n, const int32_t *d_index, int m, bool indexed, int bounce_limit, int n_spp, float *d_color,
+                       uint32_t *d_seed)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && (!d_rays || !d_color || !d_seed)) || (indexed && (m < 0 || (m > 0 && !d_index)))) return fail(c, PTMI_EINVAL, "bad ray-path arguments");
+    if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
+    if (c->scene.has_glass) return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
+    if (n == 0 || n_spp <= 0 || (indexed && m == 0)) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    const SceneState &s = c->scene;
+    PTMI_HIP(c, launch_trace_paths(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
+                                   indexed ? d_index : nullptr, m, bounce_limit, n_spp, d_color, d_seed, c->stream));
+    return PTMI_OK;
+}
+
+int ptmi_path_seeds_device(ptmi_ctx *c, uint64_t seed0, uint64_t first_index, int n, uint32_t *d_seed)
+{
+    if (!c) return PTMI_EINVAL;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n < 0 || (n > 0 && !d_seed)) return fail(c, PTMI_EINVAL, "bad ray-path arguments");
+    if (n == 0) return PTMI_OK;
+    PTMI_HIP(c, hipSetDevice(c->device));
+    PTMI_HIP(c, launch_path_seeds(seed0, first_index, n, d_seed, c->stream));
+    return PTMI_OK;
+}
+
+int ptmi_trace_paths_device(ptmi_ctx *c, const float *d_rays, int n, int bounce_limit, int n_spp, float *d_color, uint32_t *d_seed)
+{
+    return trace_paths(c, d_rays, n, nullptr, 0, false, bounce_limit, n_spp, d_color, d_seed);
+}
+
+int ptmi_trace_paths_indexed_device(ptmi_ctx *c, const float *d_rays, int n, const int32_t *d_index, int m, int bounce_limit, int n_spp, float *d_color,
+                                    uint32_t *d_seed)
+{
+    return trace_paths(c, d_rays, n, d_index, m, true, bounce_limit, n_spp, d_color, d_seed);
+}
+
 int ptmi_eval_sincos(ptmi_ctx *c, const float *x, int n, float *sin_out, float *cos_out)
 {
     if (!c) return PTMI_EINVAL;

@@ -275,6 +275,13 @@ hipError_t launch_trace_rays_indexed(SceneView scene, const BvhView *bvh, const 
                                      float *t, int32_t *idx, float *hit, hipStream_t stream);
 hipError_t launch_occluded_indexed(SceneView scene, const BvhView *bvh, const MeshView *mesh, float reach, const float *rays, const float *t_max, int n,
                                    const int32_t *index, int m, int32_t *occluded, hipStream_t stream);
+// Render Inline along a caller's rays (ptmi_trace_paths_device, ptmi_trace_paths_indexed_device; ptmi_paths.hip): one lane per ray -- per entry
+// of `index` when that is not null, an entry outside [0, n) skipped -- adds n_spp samples of traceInline to color[i] (n x 3 words) and
+// advances seed[i] (n x 4 words: a, b, c, counter).  Nothing is launched for n, m or n_spp <= 0.  path_seeds: seed[i] = genSeeds' state of
+// index first_index + i (ptmi_path_seeds_device).
+hipError_t launch_trace_paths(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, int n, const int32_t *index, int m,
+                              int bounce_limit, int n_spp, float *color, uint32_t *seed, hipStream_t stream);
+hipError_t launch_path_seeds(uint64_t seed0, uint64_t first_index, int n, uint32_t *seed, hipStream_t stream);
 // A coherent order for n rays (ptmi_ray_order_device; ptmi_ray_order.hip): order[position] = ray, ascending by (ptmi_ray_order.h's key,
 // index).  work: ray_order_bytes(n) bytes, 8-byte aligned -- the sort's scratch and the box words behind it.
 size_t ray_order_bytes(int n);

@@ -52,7 +52,8 @@ extern "C" {
                             * ptmi_group_update_spheres, ptmi_group_set_bvh_spheres, ptmi_bvh_refit_layout, ptmi_bvh_layout_morton,
                             * ptmi_bvh_read_layout); the spatial device build of a sphere hierarchy (option 17 = PTMI_OPT_BVH_DEVICE_BUILD,
                             * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial); the ray queries on device-resident rays (ptmi_trace_rays_device,
-                            * ptmi_occluded_device). */
+                            * ptmi_occluded_device); paths along device-resident rays (ptmi_trace_paths_device,
+                            * ptmi_trace_paths_indexed_device, ptmi_path_seeds_device). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -789,6 +790,37 @@ int ptmi_trace_rays_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, co
                                    float *d_t, int32_t *d_idx, float *d_hit /* may be NULL */);
 int ptmi_occluded_indexed_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m,
                                  int32_t *d_occluded);
+
+/* ---- paths along a caller's rays ---------------------------------------------- */
+/* The third question about a caller's own device-resident rays, the one only a camera could ask so far: what light arrives along this ray
+ * (traceInline, src/Scene/Trace.hs:344-383).  It serves cameras ptmi_camera cannot describe (fisheye, orthographic, thin lens), jittered
+ * primaries, light probes, sensor positions and paths continued from a caller's own first bounce.  d_rays is the ray queries' array;
+ * d_color holds n x 3 floats (r, g, b of ray i at 3 i) and d_seed n x 4 words (the SFC32 state a, b, c, counter of ray i at 4 i), both
+ * read and written.  The order, lifetime and alignment rules are those of "ray queries on the device": one launch on the context's
+ * launch stream, no host synchronisation, no device allocation, no copy; a later scene call is ordered behind it; 4-byte alignment
+ * suffices for every array (8-byte aligned rays and 16-byte aligned seeds are moved in wider pieces).
+ *   - ptmi_trace_paths_device does for ray i what ptmi_render(PTMI_INLINE) does for a pixel, with the render kernels' own arithmetic:
+ *         repeat n_spp times:  (new, seed') = traceInline bounce_limit scene ray_i seed_i;  color_i = new + color_i;  seed_i = seed'
+ *     so the primary rays of a ptmi_camera, ptmi_path_seeds_device's seeds and a zero colour give ptmi_init_output + ptmi_render's seven
+ *     planes bit for bit, and one call of n_spp samples equals n_spp calls of one.  The ray is taken as given, with a direction of any
+ *     length; a ray with a non-finite word goes wherever checkHit and the shade take it.  bounce_limit <= 0 with n_spp > 0 gives
+ *     color_i = 0 + color_i and leaves the seed as it was; n_spp <= 0 or n == 0 is PTMI_OK and touches nothing.  The scene is the context's
+ *     current one of any kind: linear, BVH or mesh.  The context's state planes, partition, camera and statistics are not touched.
+ *   - ptmi_path_seeds_device fills d_seed[i] with the state ptmi_init_output(seed0) gives pixel first_index + i of an unpartitioned image
+ *     (genSeeds, src/Util.hs:122-135).  It needs no scene (no PTMI_ESTATE); n == 0 is PTMI_OK.
+ *   - ptmi_trace_paths_indexed_device follows the indexed queries' contract: lane k < m takes i = d_index[k]; an entry outside [0, n) is
+ *     skipped, nothing is read or written for it; a position no entry names is left untouched; m == 0 is PTMI_OK.  Colour and seed are
+ *     read, modified and written, so the index must name a ray AT MOST ONCE: a ray named twice is a race between two lanes, and its
+ *     colour and seed are then undefined.  (ptmi_ray_order_device's order is a permutation and qualifies; so does a list of live rays.)
+ *   - Refusals enqueue and write nothing: PTMI_ESTATE before any scene is set (the two path entries); PTMI_EINVAL for a negative n or m,
+ *     for a NULL required pointer with a positive count, and for a scene that holds a GLASS material -- render Inline cannot split rays,
+ *     as for ptmi_render(PTMI_INLINE).
+ *   - There is no group form, as for the ray queries. */
+int ptmi_path_seeds_device(ptmi_ctx *ctx, uint64_t seed0, uint64_t first_index, int n, uint32_t *d_seed /* [n][4] */);
+int ptmi_trace_paths_device(ptmi_ctx *ctx, const float *d_rays /* [n][6] */, int n, int bounce_limit, int n_spp,
+                            float *d_color /* [n][3], in/out */, uint32_t *d_seed /* [n][4] a, b, c, counter; in/out */);
+int ptmi_trace_paths_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, const int32_t *d_index, int m,
+                                    int bounce_limit, int n_spp, float *d_color, uint32_t *d_seed);
 
 /* ---- point queries (the reference's unit-test surface) ------------------------ */
 /* Evaluates distanceTo / hit (src/Scene/Intersection.hs:16-64) on the DEVICE for n independent
