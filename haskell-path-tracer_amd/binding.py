@@ -147,6 +147,11 @@ SYMBOLS = {
     "ptmi_path_seeds_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
     "ptmi_trace_paths_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ptmi_trace_paths_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ptmi_bounce_rays_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptmi_bounce_rays_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptmi_live_rays_bytes": (C.c_size_t, [C.c_int]),
+    "ptmi_live_rays_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t]),
+    "ptmi_live_rays": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
@@ -295,6 +300,40 @@ def ray_order(rays):
 def ray_order_bytes(n):
     """ptmi_ray_order_bytes: the workspace ptmi_ray_order_device needs for n rays."""
     return int(load_library().ptmi_ray_order_bytes(int(n)))
+
+
+LIVE_RAYS_MAX = 1 << 22                                    # PTMI_LIVE_RAYS_MAX
+
+
+def live_rays_bytes(count):
+    """ptmi_live_rays_bytes: the workspace ptmi_live_rays_device needs for that many candidates."""
+    return int(load_library().ptmi_live_rays_bytes(int(count)))
+
+
+def live_rays(throughput, index=None, out=None):
+    """ptmi_live_rays: the list ptmi_live_rays_device gives (host code, no device) -> (live, count).  throughput: float32 (n, 3); index:
+    int32 (m,) or None for the candidates 0 .. n - 1.  live: int32, one entry per candidate -- those inside [0, n) whose throughput is
+    not nearZero, in candidate order, then -1 -- written into `out` when given (which may be `index` itself)."""
+    t = np.asarray(throughput)
+    if t.dtype != np.float32 or t.ndim != 2 or t.shape[1] != 3 or not t.flags.c_contiguous:
+        raise ValueError("throughput must be a contiguous float32 array of shape (n, 3), not %s %r" % (t.dtype, t.shape))
+    if index is not None:
+        index = np.asarray(index)
+        if index.dtype != np.int32 or index.ndim != 1 or not index.flags.c_contiguous:
+            raise ValueError("index must be a contiguous int32 array of shape (m,), not %s %r" % (index.dtype, index.shape))
+    candidates = t.shape[0] if index is None else index.shape[0]
+    if out is None:
+        out = np.zeros(candidates, np.int32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (candidates,) or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous int32 array of shape (%d,)" % candidates)
+    if candidates == 0:                                  # (an empty index has no pointer, and a NULL index means every ray)
+        return out, 0
+    count = C.c_int32(0)
+    rc = load_library().ptmi_live_rays(_ptr(t) if t.size else None, t.shape[0], _ptr(index) if index is not None and index.size else None,
+                                       index.shape[0] if index is not None else 0, _ptr(out) if out.size else None, C.byref(count))
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_live_rays")
+    return out, int(count.value)
 
 
 def _device_rows(t, words, what):
@@ -878,6 +917,82 @@ class Context:
         else:
             self._check(self._lib.ptmi_trace_paths_indexed_device(self._h, d_rays, n, d_index, int(index.shape[0]), int(bounce_limit), int(spp), d_color, d_seed))
         return color
+
+    # -- stepped paths: one bounce at a time, and the live rays ----------------------------
+    def bounce_rays(self, rays, seeds, throughput, radiance, index=None, hit=False, out=None):
+        """ptmi_bounce_rays_device: one prepareRay for every ray, on the context's stream, nothing leaving the device.  rays (n, 6) float32,
+        seeds (n, 4) of any 4-byte integer dtype, throughput and radiance (n, 3) float32: contiguous device tensors, all CHANGED IN PLACE --
+        a ray whose throughput is nearZero or that hits nothing gets throughput 0 and keeps ray, radiance and seed; a ray that hits gets
+        radiance += emittance * throughput, throughput *= tmod, the next ray and the advanced seed.  From throughput 1 and radiance 0,
+        k calls are trace_paths(bounce_limit=k) bit for bit.
+        -> None, or (t, idx, hit) -- trace_rays' words for the INCOMING rays, the miss record (0, -1, zeros) where a ray missed or was not
+        traced -- with hit=True (allocated on the rays' device) or out=(t, idx, hit), the caller's own, any of the three None.
+        index: an int32 device tensor (m,) -- ptmi_bounce_rays_indexed_device: only the rays it names are stepped (ray_order's order, or
+        live_rays' padded list), each AT MOST ONCE; an entry outside [0, n) is skipped.  Outputs allocated here are then filled with the
+        miss record first, by torch on its current stream, as for trace_rays; a caller's out= is left as it is at the other positions."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        d_seed = self._seed_tensor(seeds, n, "seeds")
+        d_throughput = _device_tensor(throughput, "float32", (n, 3), "throughput")
+        d_radiance = _device_tensor(radiance, "float32", (n, 3), "radiance")
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        outs = None
+        if out is not None:
+            if len(out) != 3:
+                raise ValueError("out must be (t, idx, hit), any of them None")
+            outs = tuple(out)
+        elif hit:
+            import torch
+            if index is None:
+                outs = (torch.empty(n, dtype=torch.float32, device=rays.device), torch.empty(n, dtype=torch.int32, device=rays.device),
+                        torch.empty((n, 6), dtype=torch.float32, device=rays.device))
+            else:
+                outs = (torch.zeros(n, dtype=torch.float32, device=rays.device), torch.full((n,), -1, dtype=torch.int32, device=rays.device),
+                        torch.zeros((n, 6), dtype=torch.float32, device=rays.device))
+        d_t = d_idx = d_hit = None
+        if outs is not None:
+            d_t = _device_tensor(outs[0], "float32", (n,), "t") if outs[0] is not None else None
+            d_idx = _device_tensor(outs[1], "int32", (n,), "idx") if outs[1] is not None else None
+            d_hit = _device_tensor(outs[2], "float32", (n, 6), "hit") if outs[2] is not None else None
+        if index is None:
+            self._check(self._lib.ptmi_bounce_rays_device(self._h, d_rays, n, d_throughput, d_radiance, d_seed, d_t, d_idx, d_hit))
+        else:
+            self._check(self._lib.ptmi_bounce_rays_indexed_device(self._h, d_rays, n, d_index, int(index.shape[0]), d_throughput, d_radiance, d_seed,
+                                                                  d_t, d_idx, d_hit))
+        return outs
+
+    def live_rays(self, throughput, index=None, out=None, count=None, work=None):
+        """ptmi_live_rays_device: the rays that are still alive, on the context's stream, nothing leaving the device -> `out`, an int32 device
+        tensor with one entry per candidate: the candidates -- index's entries, or 0 .. n - 1 -- inside [0, n) whose throughput (n, 3) is
+        not nearZero, in candidate order, then -1: the index= of bounce_rays, trace_rays, occluded and trace_paths, with no host wait.
+        out may be `index` itself (in place); count: an int32 device tensor (1,) that receives the number of live rays; work: a uint8
+        device tensor of at least live_rays_bytes(candidates) elements, 8-byte aligned, scratch while the call is in flight.  out and work
+        are allocated with torch.empty on the throughput's device by default, as ray_order's are.  No scene is needed."""
+        d_throughput = _device_tensor(throughput, "float32", (None, 3), "throughput")
+        n = int(throughput.shape[0])
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        m = int(index.shape[0]) if index is not None else 0
+        candidates = m if index is not None else n
+        d_count = _device_tensor(count, "int32", (1,), "count") if count is not None else None
+        if out is not None:
+            _device_tensor(out, "int32", (candidates,), "out")
+        if work is not None:
+            _device_tensor(work, "uint8", (None,), "work")
+        need = int(self._lib.ptmi_live_rays_bytes(candidates))
+        if out is None or work is None:
+            import torch
+            if out is None:
+                out = torch.empty(candidates, dtype=torch.int32, device=throughput.device)
+            if work is None:
+                work = torch.empty(need, dtype=torch.uint8, device=throughput.device)
+        d_out = _device_tensor(out, "int32", (candidates,), "out")
+        d_work = _device_tensor(work, "uint8", (None,), "work")
+        if int(work.shape[0]) < need:
+            raise ValueError("work must hold live_rays_bytes(%d) = %d bytes, not %d" % (candidates, need, int(work.shape[0])))
+        if candidates == 0:                              # (an empty index has no pointer, and a NULL index means every ray)
+            return out
+        self._check(self._lib.ptmi_live_rays_device(self._h, d_throughput, n, d_index, m, d_out, d_count, d_work, int(work.shape[0])))
+        return out
 
     def eval_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -282,6 +282,16 @@ hipError_t launch_occluded_indexed(SceneView scene, const BvhView *bvh, const Me
 hipError_t launch_trace_paths(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, int n, const int32_t *index, int m,
                               int bounce_limit, int n_spp, float *color, uint32_t *seed, hipStream_t stream);
 hipError_t launch_path_seeds(uint64_t seed0, uint64_t first_index, int n, uint32_t *seed, hipStream_t stream);
+// One bounce of a caller's paths (ptmi_bounce_rays_device, ptmi_bounce_rays_indexed_device; ptmi_bounce.hip): one lane per ray -- per entry of
+// `index` when that is not null, an entry outside [0, n) skipped -- does one prepareRay on (rays[i], radiance[i], throughput[i], seed[i]) in
+// place and writes the incoming ray's hit words to those of t, idx, hit that are not null.  Nothing is launched for n or m <= 0.
+hipError_t launch_bounce_rays(SceneView scene, const BvhView *bvh, const MeshView *mesh, float *rays, int n, const int32_t *index, int m, float *throughput,
+                              float *radiance, uint32_t *seed, float *t, int32_t *idx, float *hit, hipStream_t stream);
+// The live list (ptmi_live_rays_device; ptmi_bounce.hip): live[0 .. *n_live) = the candidates -- index[0 .. count), or 0 .. count - 1 when index
+// is null -- inside [0, n) whose throughput is not nearZero, in candidate order; -1 behind them up to count.  n_live may be null; live may be
+// index.  work: live_rays_bytes(count) bytes, 8-byte aligned.
+size_t live_rays_bytes(int count);
+hipError_t launch_live_rays(const float *throughput, int n, const int32_t *index, int count, int32_t *live, int32_t *n_live, void *work, hipStream_t stream);
 // A coherent order for n rays (ptmi_ray_order_device; ptmi_ray_order.hip): order[position] = ray, ascending by (ptmi_ray_order.h's key,
 // index).  work: ray_order_bytes(n) bytes, 8-byte aligned -- the sort's scratch and the box words behind it.
 size_t ray_order_bytes(int n);

@@ -53,7 +53,8 @@ extern "C" {
                             * ptmi_bvh_read_layout); the spatial device build of a sphere hierarchy (option 17 = PTMI_OPT_BVH_DEVICE_BUILD,
                             * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial); the ray queries on device-resident rays (ptmi_trace_rays_device,
                             * ptmi_occluded_device); paths along device-resident rays (ptmi_trace_paths_device,
-                            * ptmi_trace_paths_indexed_device, ptmi_path_seeds_device). */
+                            * ptmi_trace_paths_indexed_device, ptmi_path_seeds_device); those paths one bounce at a time and the list
+                            * of live rays (ptmi_bounce_rays_device, ptmi_bounce_rays_indexed_device, ptmi_live_rays_device). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -821,6 +822,55 @@ int ptmi_trace_paths_device(ptmi_ctx *ctx, const float *d_rays /* [n][6] */, int
                             float *d_color /* [n][3], in/out */, uint32_t *d_seed /* [n][4] a, b, c, counter; in/out */);
 int ptmi_trace_paths_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, const int32_t *d_index, int m,
                                     int bounce_limit, int n_spp, float *d_color, uint32_t *d_seed);
+
+/* ---- stepped paths: one bounce at a time, and the live rays -------------------- */
+/* ptmi_trace_paths_device's loop is closed.  These entries hand a caller the one function that loop iterates and the list of rays that
+ * are still alive, so that an integrator of the caller's own -- next-event estimation with ptmi_occluded_device between bounces, Russian
+ * roulette, a depth limit per ray, per-bounce AOVs, a light tracer, a path that stops in a region -- keeps the device's materials,
+ * rotation and SFC32 draws.  The order, lifetime and alignment rules are those of "ray queries on the device": everything is enqueued on
+ * the context's launch stream, no host synchronisation, no device allocation, no copy to the host; a later scene call is ordered behind
+ * the call; 4-byte alignment suffices for every array (8-byte aligned rays and hit records and 16-byte aligned seeds are moved in wider
+ * pieces).  The context's state planes, partition, camera and statistics are not touched.  There is no group form.
+ *   - ptmi_bounce_rays_device does, for ray i, exactly one prepareRay (src/Scene/Trace.hs:359-383) on (ray_i, radiance_i, throughput_i,
+ *     seed_i), all four read and written in place, with the render kernels' own arithmetic:
+ *       FROZEN OR MISSED -- nearZero throughput_i (the ray is then not traced; a NaN throughput is not nearZero), or checkHit scene ray_i
+ *         is Nothing:  throughput_i = (0, 0, 0); ray, radiance and seed keep every bit; the optional outputs get the miss record
+ *         (t 0, idx -1, six zeros).
+ *       HIT -- computeRay:  radiance_i += emittance * throughput_i;  throughput_i *= tmod;  ray_i = (hit + next ^* epsilon, next);  the
+ *         seed advances by genVec's draws; the optional outputs receive ptmi_trace_rays_device's words for the INCOMING ray: t, the
+ *         primitive, and the position and normal that were shaded.
+ *     So from throughput 1 and radiance 0, k calls give traceInline k's result (as 0 + radiance) and seed bit for bit, and
+ *     ptmi_trace_paths_device(limit k, 1 spp) from a zero colour.  d_t, d_idx and d_hit may each be NULL.
+ *   - ptmi_bounce_rays_indexed_device: lane k < m takes i = d_index[k]; an entry outside [0, n) is skipped, nothing is read or written for
+ *     it; a position no entry names is left untouched.  The state is read, modified and written, so the index must name a ray AT MOST
+ *     ONCE: a ray named twice is a race between two lanes.  (ptmi_ray_order_device's order and ptmi_live_rays_device's list qualify: the
+ *     list's -1 padding is skipped.)
+ *   - Refusals of the two step entries are those of ptmi_trace_paths_device, and nothing is enqueued or written: PTMI_ESTATE before any
+ *     scene is set; PTMI_EINVAL for a negative n or m, for a NULL required pointer with a positive count, and for a scene that holds a
+ *     GLASS material.  n == 0 or m == 0 is PTMI_OK and touches nothing.
+ *   - ptmi_live_rays_device lists the rays that are still alive.  The candidates are d_index[0 .. m), or 0 .. n - 1 when d_index is NULL
+ *     (m is then not looked at beyond its sign); a candidate is live when it lies in [0, n) and its throughput is not nearZero.  d_live
+ *     receives the live candidates in candidate order -- the compaction is stable and deterministic, so a coherent order stays coherent
+ *     -- and -1 in every remaining entry up to the candidate count; d_count, unless NULL, receives their number.  IN PLACE: d_live may be
+ *     the same array as d_index (the candidates are copied into the workspace before the first entry is written); any other overlap is
+ *     undefined.  d_work: ptmi_live_rays_bytes(candidate count) bytes, 8-byte aligned, scratch while the call is in flight.  It needs no
+ *     scene (no PTMI_ESTATE).  Several small launches (count, scan, scatter), none of which waits on another workgroup.
+ *     Refusals, nothing enqueued or written: PTMI_EINVAL for a negative n or m, for a NULL d_live or d_work or (with n > 0) d_throughput
+ *     with a positive candidate count, for a d_work that is not 8-byte aligned, for work_bytes below ptmi_live_rays_bytes; PTMI_ELIMIT
+ *     for a candidate count above PTMI_LIVE_RAYS_MAX.  Zero candidates is PTMI_OK and touches nothing.
+ *   - ptmi_live_rays is its host twin: host arrays, no context, no device, no workspace; the same list, the same refusals, and `live`
+ *     may be `index`.  It is the definition the device list is tested against. */
+#define PTMI_LIVE_RAYS_MAX (1 << 22)
+int ptmi_bounce_rays_device(ptmi_ctx *ctx, float *d_rays /* [n][6], in/out */, int n, float *d_throughput /* [n][3], in/out */,
+                            float *d_radiance /* [n][3], in/out */, uint32_t *d_seed /* [n][4], in/out */,
+                            float *d_t, int32_t *d_idx, float *d_hit /* [n][6]; each of the three may be NULL */);
+int ptmi_bounce_rays_indexed_device(ptmi_ctx *ctx, float *d_rays, int n, const int32_t *d_index, int m, float *d_throughput,
+                                    float *d_radiance, uint32_t *d_seed, float *d_t, int32_t *d_idx, float *d_hit);
+size_t ptmi_live_rays_bytes(int count);   /* workspace for that many candidates; 0 for count <= 0 */
+int ptmi_live_rays_device(ptmi_ctx *ctx, const float *d_throughput /* [n][3] */, int n, const int32_t *d_index /* [m] or NULL */, int m,
+                          int32_t *d_live /* [m], or [n] when d_index is NULL */, int32_t *d_count /* one word, may be NULL */,
+                          void *d_work, size_t work_bytes);
+int ptmi_live_rays(const float *throughput, int n, const int32_t *index, int m, int32_t *live, int32_t *count);
 
 /* ---- point queries (the reference's unit-test surface) ------------------------ */
 /* Evaluates distanceTo / hit (src/Scene/Intersection.hs:16-64) on the DEVICE for n independent
