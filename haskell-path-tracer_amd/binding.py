@@ -152,6 +152,9 @@ SYMBOLS = {
     "ptmi_live_rays_bytes": (C.c_size_t, [C.c_int]),
     "ptmi_live_rays_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t]),
     "ptmi_live_rays": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "ptmi_trace_streams_bytes": (C.c_size_t, [C.c_int]),
+    "ptmi_trace_streams_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t]),
+    "ptmi_trace_streams_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t]),
     "ptmi_eval_sincos": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ptmi_eval_quaternion": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
@@ -993,6 +996,48 @@ class Context:
             return out
         self._check(self._lib.ptmi_live_rays_device(self._h, d_throughput, n, d_index, m, d_out, d_count, d_work, int(work.shape[0])))
         return out
+
+    # -- render Streams along a caller's rays -----------------------------------------------
+    def trace_streams_bytes(self, count):
+        """ptmi_trace_streams_bytes: the workspace trace_streams needs for that many lanes on a scene with GLASS."""
+        return int(self._lib.ptmi_trace_streams_bytes(int(count)))
+
+    def trace_streams(self, rays, seeds, spp=1, color=None, index=None, lost=None, work=None):
+        """ptmi_trace_streams_device: render Streams along the caller's rays, on the context's stream, nothing leaving the device -- for ray
+        i, spp times, the sample's ray tree is walked depth first from ray_i with seed_i: every hit adds emittance * throughput to color_i,
+        a GLASS hit splits the ray, no bounce limit (nearZero, a miss or OPT_STREAM_STEP_CAP ends a lineage), the seed rule of
+        OPT_STREAMS_SEED_RULE; then seed_i advances one draw.  rays, seeds, color and index as trace_paths takes them; -> color.
+        lost: an int64 device tensor (2,), ADDED to: the rays the step cap cut and the children a full stack dropped.
+        work: a uint8 device tensor of at least trace_streams_bytes(lanes) elements, 16-byte aligned, scratch while the call is in flight
+        (lanes: the index's length, or n); only a scene with GLASS uses it.  The binding cannot see whether the scene holds GLASS, so it
+        allocates one with torch.empty on the rays' device when none is given and keeps it for later calls."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        d_seed = self._seed_tensor(seeds, n, "seeds")
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        d_lost = _device_tensor(lost, "int64", (2,), "lost") if lost is not None else None
+        if work is not None:
+            _device_tensor(work, "uint8", (None,), "work")
+        if color is None:
+            import torch
+            color = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        d_color = _device_tensor(color, "float32", (n, 3), "color")
+        lanes = int(index.shape[0]) if index is not None else n
+        if lanes == 0 or n == 0 or int(spp) <= 0:       # (an empty index has no pointer, and nothing would be touched)
+            return color
+        if work is None:
+            need = self.trace_streams_bytes(lanes)
+            work = getattr(self, "_streams_work", None)
+            if work is None or int(work.shape[0]) < need or work.device != rays.device:
+                import torch
+                work = self._streams_work = torch.empty(need, dtype=torch.uint8, device=rays.device)
+        d_work = _device_tensor(work, "uint8", (None,), "work")
+        if index is None:
+            self._check(self._lib.ptmi_trace_streams_device(self._h, d_rays, n, int(spp), d_color, d_seed, d_lost, d_work, int(work.shape[0])))
+        else:
+            self._check(self._lib.ptmi_trace_streams_indexed_device(self._h, d_rays, n, d_index, lanes, int(spp), d_color, d_seed, d_lost, d_work,
+                                                                    int(work.shape[0])))
+        return color
 
     def eval_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

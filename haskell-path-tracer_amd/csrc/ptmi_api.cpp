@@ -83,15 +83,15 @@ static hipError_t copy_spans(ptmi_ctx *c, const CopySpan *spans, int n, bool to_
 hipError_t ptmi::copy_to_device(ptmi_ctx *c, const CopySpan *spans, int n) { return copy_spans(c, spans, n, false); }
 hipError_t ptmi::copy_to_host(ptmi_ctx *c, const CopySpan *spans, int n) { return copy_spans(c, spans, n, true); }
 
-namespace {
-
 // PTMI_SEED_AUTO: `combine new old` (the seed of the result) wherever the reference defines the outcome -- no ray-splitting
 // material -- and the accumulator's seed with GLASS, where several results of one step would race for it
-int effective_seed_rule(const ptmi_ctx *c)
+int ptmi::effective_seed_rule(const ptmi_ctx *c)
 {
     if (c->opt_seed_rule != PTMI_SEED_AUTO) return c->opt_seed_rule;
     return c->scene.has_glass ? PTMI_SEED_KEEP_ACCUMULATOR : PTMI_SEED_FROM_RESULT;
 }
+
+namespace {
 
 // PTMI_OPT_STREAMS_FORM resolved: does `render Streams` run in its stream ("wavefront") form?  AUTO: only where it pays and costs nothing that
 // was promised -- a scene with GLASS (no reference semantics, no defined addition order in Accelerate's permute either) on ONE PART of a

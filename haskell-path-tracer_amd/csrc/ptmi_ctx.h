@@ -285,6 +285,7 @@ struct RenderTarget {                                      // what a launch rend
     static RenderTarget whole(const Planes &p, int w, int h, const int64_t *sx = nullptr, const int64_t *sy = nullptr) { return {p, w, h, h, h, 1, 0, sx, sy}; }
 };
 int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
+int effective_seed_rule(const ptmi_ctx *c);               // PTMI_OPT_STREAMS_SEED_RULE resolved for the context's scene
 int launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
 constexpr size_t kItersBytes = (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int);      // sharded statistics (ptmi_kernels.h)
 // `render Streams` in its stream form (ptmi_stream_call.cpp): launch_render's branch for it

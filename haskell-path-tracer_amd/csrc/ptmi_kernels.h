@@ -287,6 +287,13 @@ hipError_t launch_path_seeds(uint64_t seed0, uint64_t first_index, int n, uint32
 // place and writes the incoming ray's hit words to those of t, idx, hit that are not null.  Nothing is launched for n or m <= 0.
 hipError_t launch_bounce_rays(SceneView scene, const BvhView *bvh, const MeshView *mesh, float *rays, int n, const int32_t *index, int m, float *throughput,
                               float *radiance, uint32_t *seed, float *t, int32_t *idx, float *hit, hipStream_t stream);
+// Render Streams along a caller's rays (ptmi_trace_streams_device, ptmi_trace_streams_indexed_device; ptmi_trace_streams.hip): one lane per
+// ray -- per entry of `index` when that is not null, an entry outside [0, n) skipped -- walks n_spp samples' ray trees depth first, adds every
+// hit to color[i] and advances seed[i].  lost: two words (truncated, dropped), added to, or null.  work: trace_streams_bytes(lanes) bytes,
+// 16-byte aligned; read and written only at a GLASS hit, so it may be null for a scene without GLASS.  Nothing is launched for n, m or n_spp <= 0.
+size_t trace_streams_bytes(int count);
+hipError_t launch_trace_streams(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, int n, const int32_t *index, int m, int n_spp,
+                                int step_cap, bool seed_from_result, float *color, uint32_t *seed, unsigned long long *lost, void *work, hipStream_t stream);
 // The live list (ptmi_live_rays_device; ptmi_bounce.hip): live[0 .. *n_live) = the candidates -- index[0 .. count), or 0 .. count - 1 when index
 // is null -- inside [0, n) whose throughput is not nearZero, in candidate order; -1 behind them up to count.  n_live may be null; live may be
 // index.  work: live_rays_bytes(count) bytes, 8-byte aligned.

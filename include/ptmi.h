@@ -872,6 +872,57 @@ int ptmi_live_rays_device(ptmi_ctx *ctx, const float *d_throughput /* [n][3] */,
                           void *d_work, size_t work_bytes);
 int ptmi_live_rays(const float *throughput, int n, const int32_t *index, int m, int32_t *live, int32_t *count);
 
+/* ---- render Streams along a caller's rays -------------------------------------- */
+/* The entries above are render Inline.  These run the library's other algorithm, render Streams (src/Scene/Trace.hs:141-191, 272-331), along
+ * a caller's own device-resident rays: no bounce limit -- a path ends by nearZero, a miss or PTMI_OPT_STREAM_STEP_CAP -- the Streams seed
+ * rule (PTMI_OPT_STREAMS_SEED_RULE), and rays that SPLIT: a scene with a GLASS material, which the Inline entries refuse, is served.
+ * d_rays, d_color and d_seed are ptmi_trace_paths_device's arrays.  The order, lifetime and alignment rules are those of "ray queries on
+ * the device": everything is enqueued on the context's launch stream, no host synchronisation, no device allocation, no copy; a later
+ * scene call is ordered behind the call; 4-byte alignment suffices for rays, colour and seeds (8-byte aligned rays and 16-byte aligned
+ * seeds are moved in wider pieces).  The context's state planes, partition, camera, dispatch order and ptmi_stats are not touched.
+ *   - ptmi_trace_streams_device does for ray i what ptmi_render(PTMI_STREAMS) in its per-pixel form does for a pixel, with the render
+ *     kernels' own arithmetic and the ray as given, with a direction of any length:
+ *         acc = color_i ; pixel_seed = seed_i
+ *         repeat n_spp times:
+ *             cur = (ray_i, throughput (1, 1, 1), seed = pixel_seed, steps = 0) ; stack empty
+ *             walk cur's ray tree depth first:
+ *                 a lineage at steps >= step cap is cut and counted (truncated); otherwise checkHit, ++steps;
+ *                 a hit:  acc = acc + emittance * throughput      (every hit, in walk order: one adder per colour word)
+ *                         under PTMI_SEED_FROM_RESULT:  pixel_seed = the seed cur carried INTO this hit
+ *                         nearZero throughput: the lineage ends
+ *                         GLASS: the two children of the formula above (PTMI_GLASS); the refraction child waits on a stack of 16 (one
+ *                                that finds it full is dropped and counted), the reflection child goes on; at steps >= step cap both
+ *                                are cut
+ *                         else:  calcNextRay; cut at steps >= step cap
+ *                 a lineage that ends pops the most recent waiting child, else the sample is over
+ *             pixel_seed advances one random @Float draw          (updateSeed)
+ *         color_i = acc ; seed_i = pixel_seed
+ *     The seed rule is the context's: PTMI_SEED_AUTO gives PTMI_SEED_FROM_RESULT without GLASS and PTMI_SEED_KEEP_ACCUMULATOR with it.  So
+ *     the primary rays of a ptmi_camera, ptmi_path_seeds_device's seeds and the planes' colours give ptmi_init_output +
+ *     ptmi_render(PTMI_STREAMS) with PTMI_FORM_PIXEL: all seven planes bit for bit, on every scene kind, with and without GLASS, under
+ *     both seed rules; and one call of n_spp samples equals n_spp calls of one.
+ *   - d_lost, unless NULL, is two 64-bit words, 8-byte aligned, ADDED to: [0] the rays the step cap cut (ptmi_stats'
+ *     stream_rays_truncated), [1] the children a full stack dropped.  They receive one atomic add per wave, and only from a wave that
+ *     lost something.
+ *   - d_work holds the first waiting children of every lane, scratch while the call is in flight.  It is required, 16-byte aligned and
+ *     at least ptmi_trace_streams_bytes(lanes) bytes only when the scene holds GLASS; without GLASS it is ignored and may be NULL.
+ *     lanes is m with an index, else n.
+ *   - ptmi_trace_streams_indexed_device follows ptmi_trace_paths_indexed_device's contract: lane k < m takes i = d_index[k]; an entry
+ *     outside [0, n) is skipped, nothing is read or written for it; a position no entry names is left untouched.  Colour and seed are
+ *     read, modified and written, so the index must name a ray AT MOST ONCE: a ray named twice is a race between two lanes.
+ *   - Refusals enqueue and write nothing: PTMI_ESTATE before any scene is set; PTMI_EINVAL for a negative n or m, for a NULL required
+ *     pointer with a positive count, for a d_lost that is not 8-byte aligned, for a d_work that is misaligned or shorter than
+ *     ptmi_trace_streams_bytes(lanes) on a GLASS scene, and for GLASS with an explicit PTMI_SEED_FROM_RESULT, as for
+ *     ptmi_render(PTMI_STREAMS).  n == 0, m == 0 or n_spp <= 0 is PTMI_OK and touches nothing.
+ *   - There is no group form, as for the ray queries. */
+size_t ptmi_trace_streams_bytes(int count);      /* workspace for that many lanes; 0 for count <= 0 */
+int ptmi_trace_streams_device(ptmi_ctx *ctx, const float *d_rays /* [n][6] */, int n, int n_spp,
+                              float *d_color /* [n][3], in/out */, uint32_t *d_seed /* [n][4], in/out */,
+                              uint64_t *d_lost /* [2]: truncated, dropped; added to; may be NULL */,
+                              void *d_work, size_t work_bytes);
+int ptmi_trace_streams_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, const int32_t *d_index, int m, int n_spp,
+                                      float *d_color, uint32_t *d_seed, uint64_t *d_lost, void *d_work, size_t work_bytes);
+
 /* ---- point queries (the reference's unit-test surface) ------------------------ */
 /* Evaluates distanceTo / hit (src/Scene/Intersection.hs:16-64) on the DEVICE for n independent
  * cases -- ray i against primitive i -- the way test/Scene/Intersection/Tests.hs:122-123
