@@ -34,7 +34,7 @@ KERNEL_UNITS = [INLINE_UNIT, "ptmi_streams_chain.hip", "ptmi_streams_tree.hip", 
                 "ptmi_query_indexed.hip", "ptmi_ray_order.hip", "ptmi_paths.hip", "ptmi_bounce.hip", "ptmi_trace_streams.hip"]
 ABLATION_UNITS = ["ptmi_inline_ablations.hip"]               # only with -DPTMI_ABLATIONS
 SOURCES = HOST_SOURCES + [BUILD_ID_UNIT] + KERNEL_UNITS + ABLATION_UNITS
-HEADERS = ["ptmi_core.h", "ptmi_ctx.h", "ptmi_kernels.h", "ptmi_device.h", "ptmi_bvh_device.h", "ptmi_bvh.h", "ptmi_bvh_box.h", "ptmi_bvh_spatial.h", "ptmi_mesh_device.h", "ptmi_query_device.h", "ptmi_mesh.h", "ptmi_mesh_box.h", "ptmi_mesh_morton.h", "ptmi_ray_order.h", "ptmi_inline_body.inc", "ptmi_streams_chain_body.inc", "ptmi_streams_tree_body.inc", "ptmi_diag.h", "ptmi_stream_form.h", "ptmi_stage.h", "ptmi_share.h",
+HEADERS = ["ptmi_core.h", "ptmi_ctx.h", "ptmi_kernels.h", "ptmi_device.h", "ptmi_bvh_device.h", "ptmi_bvh.h", "ptmi_bvh_box.h", "ptmi_bvh_spatial.h", "ptmi_mesh_device.h", "ptmi_query_device.h", "ptmi_ray_lane_device.h", "ptmi_mesh.h", "ptmi_mesh_box.h", "ptmi_mesh_morton.h", "ptmi_ray_order.h", "ptmi_inline_body.inc", "ptmi_streams_chain_body.inc", "ptmi_streams_tree_body.inc", "ptmi_diag.h", "ptmi_stream_form.h", "ptmi_stage.h", "ptmi_share.h",
            os.path.join("..", "..", "include", "ptmi.h")]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                  "-fno-fast-math", "-fno-slp-vectorize", "-DPTMI_SINCOS_FUSED=1", "-Wall", "-pthread"]

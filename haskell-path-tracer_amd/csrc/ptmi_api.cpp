@@ -91,6 +91,17 @@ int ptmi::effective_seed_rule(const ptmi_ctx *c)
     return c->scene.has_glass ? PTMI_SEED_KEEP_ACCUMULATOR : PTMI_SEED_FROM_RESULT;
 }
 
+RayCallScene ptmi::ray_call_scene(const ptmi_ctx *c)
+{
+    const SceneState &s = c->scene;
+    RayCallScene r;
+    r.scene.packed = s.packed.as<float4>(); r.scene.n_spheres = (int)s.rows.ns; r.scene.n_planes = (int)s.rows.np;
+    r.scene.share_xy = s.share_xy;
+    r.bvh = s.kind == SceneKind::Bvh ? &s.bvh : nullptr;
+    r.mesh = s.kind == SceneKind::Mesh ? &s.mesh : nullptr;
+    return r;
+}
+
 namespace {
 
 // PTMI_OPT_STREAMS_FORM resolved: does `render Streams` run in its stream ("wavefront") form?  AUTO: only where it pays and costs nothing that
@@ -936,14 +947,6 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
 
 // The ray queries on the caller's device arrays: refusals first (nothing enqueued, nothing written), then one launch on the context's
 // stream -- no synchronisation, no allocation, no scratch.
-static SceneView query_scene(const ptmi_ctx *c)
-{
-    SceneView scene;
-    scene.packed = c->scene.packed.as<float4>(); scene.n_spheres = (int)c->scene.rows.ns; scene.n_planes = (int)c->scene.rows.np;
-    scene.share_xy = c->scene.share_xy;
-    return scene;
-}
-
 int ptmi_trace_rays_device(ptmi_ctx *c, const float *d_rays, int n, float *d_t, int32_t *d_idx, float *d_hit)
 {
     if (!c) return PTMI_EINVAL;
@@ -952,9 +955,8 @@ int ptmi_trace_rays_device(ptmi_ctx *c, const float *d_rays, int n, float *d_t, 
     if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     if (n == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    PTMI_HIP(c, launch_trace_rays(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
-                                  d_t, d_idx, d_hit, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_trace_rays(r.scene, r.bvh, r.mesh, d_rays, n, d_t, d_idx, d_hit, c->stream));
     return PTMI_OK;
 }
 
@@ -966,9 +968,8 @@ int ptmi_occluded_device(ptmi_ctx *c, const float *d_rays, const float *d_t_max,
     if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     if (n == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    PTMI_HIP(c, launch_occluded(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, s.sphere_reach,
-                                d_rays, d_t_max, n, d_occluded, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_occluded(r.scene, r.bvh, r.mesh, c->scene.sphere_reach, d_rays, d_t_max, n, d_occluded, c->stream));
     return PTMI_OK;
 }
 
@@ -981,9 +982,8 @@ int ptmi_trace_rays_indexed_device(ptmi_ctx *c, const float *d_rays, int n, cons
     if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     if (n == 0 || m == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    PTMI_HIP(c, launch_trace_rays_indexed(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
-                                          d_index, m, d_t, d_idx, d_hit, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_trace_rays_indexed(r.scene, r.bvh, r.mesh, d_rays, n, d_index, m, d_t, d_idx, d_hit, c->stream));
     return PTMI_OK;
 }
 
@@ -995,9 +995,9 @@ int ptmi_occluded_indexed_device(ptmi_ctx *c, const float *d_rays, const float *
     if (!c->scene.packed.p) return fail(c, PTMI_ESTATE, "ptmi_set_scene has not been called");
     if (n == 0 || m == 0) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    PTMI_HIP(c, launch_occluded_indexed(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, s.sphere_reach,
-                                        d_rays, d_t_max, n, d_index, m, d_occluded, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_occluded_indexed(r.scene, r.bvh, r.mesh, c->scene.sphere_reach, d_rays, d_t_max, n, d_index, m,
+                                        d_occluded, c->stream));
     return PTMI_OK;
 }
 
@@ -1013,9 +1013,8 @@ static int trace_paths(ptmi_ctx *c, const float *d_rays, int n, const int32_t *d
     if (c->scene.has_glass) return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
     if (n == 0 || n_spp <= 0 || (indexed && m == 0)) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    PTMI_HIP(c, launch_trace_paths(query_scene(c), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
-                                   indexed ? d_index : nullptr, m, bounce_limit, n_spp, d_color, d_seed, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_trace_paths(r.scene, r.bvh, r.mesh, d_rays, n, indexed ? d_index : nullptr, m, bounce_limit, n_spp, d_color, d_seed, c->stream));
     return PTMI_OK;
 }
 

@@ -18,12 +18,9 @@ static int bounce_rays(ptmi_ctx *c, float *d_rays, int n, const int32_t *d_index
     if (c->scene.has_glass) return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
     if (n == 0 || (indexed && m == 0)) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    SceneView scene;
-    scene.packed = s.packed.as<float4>(); scene.n_spheres = (int)s.rows.ns; scene.n_planes = (int)s.rows.np;
-    scene.share_xy = s.share_xy;
-    PTMI_HIP(c, launch_bounce_rays(scene, s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
-                                   indexed ? d_index : nullptr, m, d_throughput, d_radiance, d_seed, d_t, d_idx, d_hit, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_bounce_rays(r.scene, r.bvh, r.mesh, d_rays, n, indexed ? d_index : nullptr, m, d_throughput, d_radiance, d_seed, d_t, d_idx, d_hit,
+                                   c->stream));
     return PTMI_OK;
 }
 

@@ -9,10 +9,10 @@
 // throughput that shortcut skips are outputs here.  A ray whose throughput is nearZero is not traced.  The optional outputs are
 // ptmi_trace_rays_device's words for the INCOMING ray: t, the primitive, the position and normal that were shaded; the miss record (0, -1,
 // six zeros) for a ray that missed or was not traced.
-//   * one lane per ray, one wave per workgroup, one kernel per scene kind as in ptmi_paths.hip: a linear scene staged in LDS without and
-//     with shared-xy runs, a linear scene too big for LDS through scalar loads, a BVH scene and a mesh scene on check_hit_bvh's LDS stack
-//     (their only static LDS: there is nothing to restart from);
-//   * the index is the wave-uniform null test of the indexed queries: lane k < m takes i = index[k] and skips an entry outside [0, n).
+//   * one lane per ray, one wave per workgroup, one kernel per scene kind (RayScene, ptmi_ray_lane_device.h, whose frame this lane stands
+//     in as the paths' does): a linear scene staged in LDS without and with shared-xy runs, a linear scene too big for LDS through scalar
+//     loads, a BVH scene and a mesh scene on check_hit_bvh's LDS stack (their only static LDS: there is nothing to restart from);
+//   * the index is lane_ray's wave-uniform null test: lane k < m takes i = index[k] and skips an entry outside [0, n).
 // Memory: rays and hit records in three 8-byte pieces when their array is 8-byte aligned, a seed in one 16-byte piece when its array is
 // 16-byte aligned, dwords otherwise; throughput and radiance three dwords each.
 //
@@ -24,17 +24,11 @@
 // candidates are read from the caller's index in the first launch alone and from the workspace afterwards, which is what lets the list be
 // written over the index it was made from.
 #define PTMI_MESH_EXACT_INLINE __forceinline__
-#include "ptmi_query_device.h"
+#include "ptmi_ray_lane_device.h"
 
 namespace ptmi {
 
 namespace {
-
-#ifndef PTMI_INLINE_WAVES
-#define PTMI_INLINE_WAVES 7      // render Inline's occupancy budget (ptmi_inline.hip)
-#endif
-
-enum class BounceScene { kLinearLds, kSharedXyLds, kLinearScalar, kBvh, kMesh };
 
 constexpr int kWideSeeds = 4;    // beside kWideRays and kWideHit: the seeds are 16-byte aligned
 
@@ -52,29 +46,19 @@ struct BounceArgs {
     float *hit;
 };
 
-template <BounceScene KIND>
+template <RayScene KIND>
 __device__ __forceinline__ void bounce_lane(const BounceArgs &a, const MeshView &uniform_mesh)
 {
-    constexpr bool LDS_SCENE = KIND == BounceScene::kLinearLds || KIND == BounceScene::kSharedXyLds;
-    extern __shared__ float4 lds_scene[];
     const int ns = a.scene.n_spheres, np = a.scene.n_planes;
-    if (LDS_SCENE) {
-        const int total = a.scene.total_f4();
-        for (int i = threadIdx.x; i < total; i += kRenderBlock) lds_scene[i] = a.scene.packed[i];
-        __syncthreads();
-    }
-    const float4 *S = LDS_SCENE ? lds_scene : a.scene.packed;
+    const float4 *S = stage_scene<KIND>(a.scene);
     const float4 *M = S + a.scene.geom_f4();
 
-    // the lane's ray: entry k of the index, or ray k
-    const int k = blockIdx.x * kRenderBlock + threadIdx.x;
-    int i = k;
-    bool valid = k < a.n;
-    if (a.index) {
-        valid = k < a.m;
-        if (valid) { i = a.index[k]; valid = (unsigned int)i < (unsigned int)a.n; }
-    }
-    if (!valid) return;
+    // (the search behind a local name: called where it is made, the hierarchies' walks compile to other code)
+    auto hit = [&](V3 o, V3 d) { return closest_hit<KIND, true, SphereFold::kStashSelect, SphereShare::kXY>(uniform_mesh, S, ns, np, a.scene.share_xy, o, d); };
+
+    int ray;
+    if (!lane_ray(a.index, a.n, a.m, ray)) return;
+    const int i = ray;
 
     float *tp = a.throughput + 3 * (size_t)i;
     V3 throughput = mk(tp[0], tp[1], tp[2]);
@@ -82,33 +66,19 @@ __device__ __forceinline__ void bounce_lane(const BounceArgs &a, const MeshView 
     HitSel h; h.t = 0.0f; h.idx = -1; h.just = false;
     if (!near_zero(throughput)) {                              // (a NaN throughput is not nearZero: the ray is traced)
         load_ray(a.rays, i, a.flags & kWideRays, o, d);
-        if constexpr (KIND == BounceScene::kLinearLds) h = check_hit<true, SphereFold::kStashSelect>(S, ns, np, o, d);
-        else if constexpr (KIND == BounceScene::kSharedXyLds) h = check_hit<true, SphereFold::kStashSelect, SphereShare::kXY>(S, ns, np, o, d, nullptr, a.scene.share_xy);
-        else if constexpr (KIND == BounceScene::kLinearScalar) h = check_hit<false, SphereFold::kStashSelect, SphereShare::kXY>(S, ns, np, o, d, nullptr, a.scene.share_xy);
-        else if constexpr (KIND == BounceScene::kBvh) h = check_hit_bvh(uniform_mesh.spheres, S, ns, np, o, d);
-        else h = check_hit_mesh(uniform_mesh, S, ns, np, o, d);
+        h = hit(o, d);
     }
     if (h.just) {
-        if constexpr (KIND == BounceScene::kMesh) mesh_hit_record(uniform_mesh, S, ns, np, h.idx, o, d, h.t, pos, normal);
-        else hit_record(S, ns, h.idx, o, d, h.t, pos, normal);
+        record_hit<KIND>(uniform_mesh, S, ns, np, h.idx, o, d, h.t, pos, normal);
         float *rp = a.radiance + 3 * (size_t)i;
         uint32_t *sp = a.seed + 4 * (size_t)i;
         V3 radiance = mk(rp[0], rp[1], rp[2]);
         Sfc32 seed;
-        if (a.flags & kWideSeeds) {
-            const uint4 w = *reinterpret_cast<const uint4 *>(sp);
-            seed.a = w.x; seed.b = w.y; seed.c = w.z; seed.counter = w.w;
-        } else {
-            seed.a = sp[0]; seed.b = sp[1]; seed.c = sp[2]; seed.counter = sp[3];
-        }
+        load_seed(sp, a.flags & kWideSeeds, seed);
         shade(M, h.idx, pos, normal, o, d, throughput, radiance, seed);          // computeRay + calcNextRay: o, d become the next ray
         store_hit(a.rays, i, a.flags & kWideRays, o, d);                          // (a ray's six words, laid out as a hit record's)
         rp[0] = radiance.x; rp[1] = radiance.y; rp[2] = radiance.z;
-        if (a.flags & kWideSeeds) {
-            *reinterpret_cast<uint4 *>(sp) = uint4{seed.a, seed.b, seed.c, seed.counter};
-        } else {
-            sp[0] = seed.a; sp[1] = seed.b; sp[2] = seed.c; sp[3] = seed.counter;
-        }
+        store_seed(sp, a.flags & kWideSeeds, seed);
     } else {
         throughput = mk(0.0f, 0.0f, 0.0f);
         h.t = 0.0f; h.idx = -1;
@@ -125,11 +95,11 @@ __device__ __forceinline__ void bounce_lane(const BounceArgs &a, const MeshView 
     {                                                                                                                                \
         bounce_lane<KIND>(a, mesh);                                                                                                  \
     }
-PTMI_BOUNCE_KERNEL(linear_lds, BounceScene::kLinearLds, PTMI_INLINE_WAVES)
-PTMI_BOUNCE_KERNEL(shared_xy_lds, BounceScene::kSharedXyLds, PTMI_INLINE_WAVES)
-PTMI_BOUNCE_KERNEL(linear_scalar, BounceScene::kLinearScalar, PTMI_INLINE_WAVES)
-PTMI_BOUNCE_KERNEL(bvh, BounceScene::kBvh, PTMI_BVH_WAVES)
-PTMI_BOUNCE_KERNEL(mesh, BounceScene::kMesh, PTMI_BVH_WAVES)
+PTMI_BOUNCE_KERNEL(linear_lds, RayScene::kLinearLds, PTMI_INLINE_WAVES)
+PTMI_BOUNCE_KERNEL(shared_xy_lds, RayScene::kSharedXyLds, PTMI_INLINE_WAVES)
+PTMI_BOUNCE_KERNEL(linear_scalar, RayScene::kLinearScalar, PTMI_INLINE_WAVES)
+PTMI_BOUNCE_KERNEL(bvh, RayScene::kBvh, PTMI_BVH_WAVES)
+PTMI_BOUNCE_KERNEL(mesh, RayScene::kMesh, PTMI_BVH_WAVES)
 #undef PTMI_BOUNCE_KERNEL
 
 // ---- the live list ----
@@ -227,8 +197,6 @@ inline LiveLayout live_layout(int count)
     return l;
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 size_t live_rays_bytes(int count) { return count <= 0 ? 0 : live_layout(count).bytes; }
@@ -265,14 +233,8 @@ hipError_t launch_bounce_rays(SceneView scene, const BvhView *bvh, const MeshVie
     a.flags = (aligned8(rays) ? kWideRays : 0) | (hit && aligned8(hit) ? kWideHit : 0) | (aligned16(seed) ? kWideSeeds : 0);
     a.throughput = throughput; a.radiance = radiance; a.seed = seed;
     a.t = t; a.idx = idx; a.hit = hit;
-    const dim3 grid(blocks_for(lanes, kRenderBlock)), block(kRenderBlock);
-    if (mesh) return launch(bounce_rays_mesh_kernel, grid, block, 0, stream, a, *mesh);
-    MeshView view{};
-    if (bvh) { view.spheres = *bvh; return launch(bounce_rays_bvh_kernel, grid, block, 0, stream, a, view); }
-    // a scene so big that staging it per wave would cost more occupancy than scalar loads cost speed is read through scalar loads (scene_fits_lds)
-    const size_t lds = (size_t)scene.total_f4() * sizeof(float4);
-    if (lds > kMaxSceneLds) return launch(bounce_rays_linear_scalar_kernel, grid, block, 0, stream, a, view);
-    return launch(scene.share_xy ? bounce_rays_shared_xy_lds_kernel : bounce_rays_linear_lds_kernel, grid, block, lds, stream, a, view);
+    return launch_by_scene(scene, bvh, mesh, bounce_rays_mesh_kernel, bounce_rays_bvh_kernel, bounce_rays_linear_scalar_kernel, bounce_rays_shared_xy_lds_kernel,
+                           bounce_rays_linear_lds_kernel, lanes, stream, a);
 }
 
 }  // namespace ptmi

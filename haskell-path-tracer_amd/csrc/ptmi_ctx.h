@@ -286,6 +286,10 @@ struct RenderTarget {                                      // what a launch rend
 };
 int check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
 int effective_seed_rule(const ptmi_ctx *c);               // PTMI_OPT_STREAMS_SEED_RULE resolved for the context's scene
+// What the launcher of a caller-ray kernel takes of the context's scene (the ray queries, the paths, the stepped paths, the ray streams):
+// the packed rows, and the hierarchy of a BVH scene or of a mesh scene -- null otherwise
+struct RayCallScene { SceneView scene; const BvhView *bvh; const MeshView *mesh; };
+RayCallScene ray_call_scene(const ptmi_ctx *c);
 int launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
 constexpr size_t kItersBytes = (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int);      // sharded statistics (ptmi_kernels.h)
 // `render Streams` in its stream form (ptmi_stream_call.cpp): launch_render's branch for it

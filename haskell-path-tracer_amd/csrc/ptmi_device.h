@@ -6,7 +6,8 @@
 //   ptmi_streams_tree.hip    render Streams with ray splitting, one tree per pixel
 //   ptmi_stream_primary.hip / ptmi_stream_pixels.hip / ptmi_stream_split.hip   the stream ("wavefront") form (ptmi_stream_form.h)
 //   ptmi_small.hip           seeds, createWith, present, stitch, dispatch order, point queries
-//   ptmi_query.hip           the ray queries on device-resident rays: closest hit, occlusion (ptmi_query_device.h)
+//   ptmi_query.hip           the ray queries on device-resident rays: closest hit, occlusion (ptmi_query_device.h), and with the other kernels along a
+//                            caller's rays -- ptmi_query_indexed.hip, ptmi_paths.hip, ptmi_bounce.hip, ptmi_trace_streams.hip -- ptmi_ray_lane_device.h
 // Everything here is in an unnamed namespace: each unit gets its own copy, nothing is linked across units (no -fgpu-rdc).
 // Diagnostic builds (-DPTMI_*_STATS) live in ptmi_diag.h; the kernels only call its probes, which are empty otherwise.
 #pragma once

@@ -11,21 +11,17 @@
 //   * one kernel per scene kind: a linear scene staged in LDS, without and with shared-xy runs (as launch_linear chooses), a linear scene
 //     too big for LDS through scalar loads, a BVH scene and a mesh scene on check_hit_bvh's LDS stack;
 //   * the index is a wave-uniform null test: lane k < m takes i = index[k] and skips an entry outside [0, n).
-// Memory: a ray as ptmi_query_device.h loads it (three 8-byte loads when the array is 8-byte aligned, six dwords otherwise); the seed one
+// The frame around the loop -- the scene kinds, the staging, the words held per lane, the search by kind, the lane's ray, the seed's load
+// and store, the launcher's choice -- is ptmi_ray_lane_device.h's, shared with ptmi_bounce.hip and ptmi_trace_streams.hip.
+// Memory: a ray as load_ray loads it (three 8-byte loads when the array is 8-byte aligned, six dwords otherwise); the seed one
 // 16-byte load and store when its array is 16-byte aligned (four dwords otherwise); the colour three dwords, 12 bytes apart.
 // The mesh scene's literal fold is inlined as in ptmi_query.hip: no kernel of this unit has any scratch.
 #define PTMI_MESH_EXACT_INLINE __forceinline__
-#include "ptmi_query_device.h"
+#include "ptmi_ray_lane_device.h"
 
 namespace ptmi {
 
 namespace {
-
-#ifndef PTMI_INLINE_WAVES
-#define PTMI_INLINE_WAVES 7      // render Inline's occupancy budget (ptmi_inline.hip)
-#endif
-
-enum class PathScene { kLinearLds, kSharedXyLds, kLinearScalar, kBvh, kMesh };
 
 struct PathArgs {
     SceneView scene;
@@ -38,73 +34,31 @@ struct PathArgs {
     uint32_t *seed;              // [n][4]: a, b, c, counter
 };
 
-template <PathScene KIND>
+template <RayScene KIND>
 __device__ __forceinline__ void trace_path_lane(const PathArgs &a, const MeshView &uniform_mesh)
 {
-    constexpr bool LDS_SCENE = KIND == PathScene::kLinearLds || KIND == PathScene::kSharedXyLds;
     __shared__ float path_const[10][kRenderBlock];          // per-lane restart record (see below)
-    extern __shared__ float4 lds_scene[];
     const int ns = a.scene.n_spheres, np = a.scene.n_planes;
-    if (LDS_SCENE) {
-        const int total = a.scene.total_f4();
-        for (int i = threadIdx.x; i < total; i += kRenderBlock) lds_scene[i] = a.scene.packed[i];
-        __syncthreads();
-    }
-    const float4 *S = LDS_SCENE ? lds_scene : a.scene.packed;
-    int materials = a.scene.geom_f4();
-    if constexpr (KIND == PathScene::kMesh) asm volatile("v_mov_b32 %0, %1" : "=v"(materials) : "s"(a.scene.geom_f4()));     // (per lane, as the boxes below)
-    const float4 *M = S + materials;
-    // (the hierarchies' kernels are short of scalar registers, not of vector ones: the boxes of the admission tests, twelve wave-uniform words
-    // that only ever meet a lane's own origin, are held per lane there, so that no scalar register spills into lanes)
-    MeshView mesh = uniform_mesh;
-    if constexpr (KIND == PathScene::kBvh || KIND == PathScene::kMesh) {
-        auto per_lane = [](float uniform) { float v; asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(uniform)); return v; };
-        for (int w = 0; w < 3; ++w) {
-            mesh.spheres.lo[w] = per_lane(uniform_mesh.spheres.lo[w]); mesh.spheres.hi[w] = per_lane(uniform_mesh.spheres.hi[w]);
-            if constexpr (KIND == PathScene::kMesh) { mesh.lo[w] = per_lane(uniform_mesh.lo[w]); mesh.hi[w] = per_lane(uniform_mesh.hi[w]); }
-        }
-    }
-    auto hit = [&](V3 o, V3 d) -> HitSel {
-        if constexpr (KIND == PathScene::kLinearLds) return check_hit<true, SphereFold::kStashSelect>(S, ns, np, o, d);
-        else if constexpr (KIND == PathScene::kSharedXyLds) return check_hit<true, SphereFold::kStashSelect, SphereShare::kXY>(S, ns, np, o, d, nullptr, a.scene.share_xy);
-        else if constexpr (KIND == PathScene::kLinearScalar) return check_hit<false, SphereFold::kStashSelect, SphereShare::kXY>(S, ns, np, o, d, nullptr, a.scene.share_xy);
-        else if constexpr (KIND == PathScene::kBvh) return check_hit_bvh(mesh.spheres, S, ns, np, o, d);
-        else return check_hit_mesh(mesh, S, ns, np, o, d);
-    };
-    auto record = [&](int idx, V3 o, V3 d, float t, V3 &p, V3 &n) {
-        if constexpr (KIND == PathScene::kMesh) mesh_hit_record(mesh, S, ns, np, idx, o, d, t, p, n);
-        else hit_record(S, ns, idx, o, d, t, p, n);
-    };
+    const float4 *S = stage_scene<KIND>(a.scene);
+    // (a mesh kernel's counts and limits are held per lane, as its boxes: per_lane)
+    const float4 *M = S + (is_mesh(KIND) ? per_lane(a.scene.geom_f4()) : a.scene.geom_f4());
+    const MeshView mesh = per_lane_view<KIND>(uniform_mesh, std::false_type{});
+    // (the record behind a local name, the search called where it is made: the shapes that keep these kernels' code)
+    auto record = [&](int idx, V3 o, V3 d, float t, V3 &p, V3 &n) { record_hit<KIND>(mesh, S, ns, np, idx, o, d, t, p, n); };
 
-    // the lane's ray: entry k of the index, or ray k
-    const int k = blockIdx.x * kRenderBlock + threadIdx.x;
-    int i = k;
-    bool valid = k < a.n;
-    if (a.index) {
-        valid = k < a.m;
-        if (valid) { i = a.index[k]; valid = (unsigned int)i < (unsigned int)a.n; }
-    }
-    if (!valid) return;
+    int ray;
+    if (!lane_ray(a.index, a.n, a.m, ray)) return;
+    const int i = ray;
 
     V3 origin, primary;
     load_ray(a.rays, i, a.flags & kWideRays, origin, primary);
     float *c = a.color + 3 * (size_t)i;
     uint32_t *sp = a.seed + 4 * (size_t)i;
     V3 acc = mk(c[0], c[1], c[2]);
-    // (whether the seeds are 16-byte aligned, asked of the lane's own address: every lane answers alike, and no flag lives in a scalar
-    // register from here to the store)
     Sfc32 seed;
-    if ((reinterpret_cast<uintptr_t>(sp) & 15u) == 0) {
-        const uint4 w = *reinterpret_cast<const uint4 *>(sp);
-        seed.a = w.x; seed.b = w.y; seed.c = w.z; seed.counter = w.w;
-    } else {
-        seed.a = sp[0]; seed.b = sp[1]; seed.c = sp[2]; seed.counter = sp[3];
-    }
-    int limit = a.bounce_limit, n_spp = a.n_spp;
-    if constexpr (KIND == PathScene::kMesh) {                 // (per lane, as the boxes)
-        asm volatile("v_mov_b32 %0, %1" : "=v"(limit) : "s"(a.bounce_limit));
-        asm volatile("v_mov_b32 %0, %1" : "=v"(n_spp) : "s"(a.n_spp));
-    }
+    load_seed(sp, seed_is_wide(sp), seed);
+    const int limit = is_mesh(KIND) ? per_lane(a.bounce_limit) : a.bounce_limit;
+    const int n_spp = is_mesh(KIND) ? per_lane(a.n_spp) : a.n_spp;
 
     {
         // iterate 0 (limit <= 0): every sample returns (0, seed); new + old (the launcher sends n_spp > 0 only), and no trip of the loop.
@@ -158,7 +112,7 @@ __device__ __forceinline__ void trace_path_lane(const PathArgs &a, const MeshVie
                 state = (it >= limit || near_zero(throughput)) ? kOver : kHasRay;
             }
             if (state == kHasRay) {
-                const HitSel h = hit(pos, d);
+                const HitSel h = closest_hit<KIND, true, SphereFold::kStashSelect, SphereShare::kXY>(mesh, S, ns, np, a.scene.share_xy, pos, d);
                 const bool first = s < -1;
                 if (h.just) {
                     record(h.idx, pos, d, h.t, pos, normal);
@@ -185,11 +139,7 @@ __device__ __forceinline__ void trace_path_lane(const PathArgs &a, const MeshVie
     }
 
     c[0] = acc.x; c[1] = acc.y; c[2] = acc.z;
-    if ((reinterpret_cast<uintptr_t>(sp) & 15u) == 0) {
-        *reinterpret_cast<uint4 *>(sp) = uint4{seed.a, seed.b, seed.c, seed.counter};
-    } else {
-        sp[0] = seed.a; sp[1] = seed.b; sp[2] = seed.c; sp[3] = seed.counter;
-    }
+    store_seed(sp, seed_is_wide(sp), seed);
 }
 
 // One kernel per scene kind, under a name that says which (a BVH scene's view travels in the mesh view's sphere part)
@@ -198,11 +148,11 @@ __device__ __forceinline__ void trace_path_lane(const PathArgs &a, const MeshVie
     {                                                                                                                                \
         trace_path_lane<KIND>(a, mesh);                                                                                              \
     }
-PTMI_PATH_KERNEL(linear_lds, PathScene::kLinearLds, PTMI_INLINE_WAVES)
-PTMI_PATH_KERNEL(shared_xy_lds, PathScene::kSharedXyLds, PTMI_INLINE_WAVES)
-PTMI_PATH_KERNEL(linear_scalar, PathScene::kLinearScalar, PTMI_INLINE_WAVES)
-PTMI_PATH_KERNEL(bvh, PathScene::kBvh, PTMI_BVH_WAVES)
-PTMI_PATH_KERNEL(mesh, PathScene::kMesh, PTMI_BVH_WAVES)
+PTMI_PATH_KERNEL(linear_lds, RayScene::kLinearLds, PTMI_INLINE_WAVES)
+PTMI_PATH_KERNEL(shared_xy_lds, RayScene::kSharedXyLds, PTMI_INLINE_WAVES)
+PTMI_PATH_KERNEL(linear_scalar, RayScene::kLinearScalar, PTMI_INLINE_WAVES)
+PTMI_PATH_KERNEL(bvh, RayScene::kBvh, PTMI_BVH_WAVES)
+PTMI_PATH_KERNEL(mesh, RayScene::kMesh, PTMI_BVH_WAVES)
 #undef PTMI_PATH_KERNEL
 
 // genSeeds for a caller's rays: seed i is the state ptmi_init_output(seed0) gives pixel first_index + i of an unpartitioned image (seed_kernel)
@@ -219,8 +169,6 @@ __global__ void __launch_bounds__(kBlock) path_seeds_kernel(uint64_t seed0, uint
         sp[0] = s.a; sp[1] = s.b; sp[2] = s.c; sp[3] = s.counter;
     }
 }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -240,14 +188,8 @@ hipError_t launch_trace_paths(SceneView scene, const BvhView *bvh, const MeshVie
     a.bounce_limit = bounce_limit; a.n_spp = n_spp;
     a.flags = aligned8(rays) ? kWideRays : 0;
     a.color = color; a.seed = seed;
-    const dim3 grid(blocks_for(lanes, kRenderBlock)), block(kRenderBlock);
-    if (mesh) return launch(trace_paths_mesh_kernel, grid, block, 0, stream, a, *mesh);
-    MeshView view{};
-    if (bvh) { view.spheres = *bvh; return launch(trace_paths_bvh_kernel, grid, block, 0, stream, a, view); }
-    // a scene so big that staging it per wave would cost more occupancy than scalar loads cost speed is read through scalar loads (scene_fits_lds)
-    const size_t lds = (size_t)scene.total_f4() * sizeof(float4);
-    if (lds > kMaxSceneLds) return launch(trace_paths_linear_scalar_kernel, grid, block, 0, stream, a, view);
-    return launch(scene.share_xy ? trace_paths_shared_xy_lds_kernel : trace_paths_linear_lds_kernel, grid, block, lds, stream, a, view);
+    return launch_by_scene(scene, bvh, mesh, trace_paths_mesh_kernel, trace_paths_bvh_kernel, trace_paths_linear_scalar_kernel, trace_paths_shared_xy_lds_kernel,
+                           trace_paths_linear_lds_kernel, lanes, stream, a);
 }
 
 }  // namespace ptmi

@@ -1,6 +1,6 @@
 // ptmi_query_device.h -- the ANY-HIT walks behind ptmi_occluded_device: "is anything in the way before t_max", over a linear scene, a BVH
-// scene and a mesh scene, and behind them what one lane of a ray query does with one ray (trace_ray, occluded_ray).  Included by
-// ptmi_query.hip and ptmi_query_indexed.hip.  DESIGN.md 5.9 summarises what follows.
+// scene and a mesh scene (occluded_linear, occluded_bvh, occluded_mesh).  Included by ptmi_ray_lane_device.h, where a lane of a ray query
+// calls them (occluded_ray).  DESIGN.md 5.9 summarises what follows.
 #pragma once
 
 #include "ptmi_mesh_device.h"
@@ -158,92 +158,6 @@ __device__ __forceinline__ bool occluded_mesh(const MeshView &M, ScenePtr S, int
     }
     if (found != kAnyFull) return found == kAnyHit;
     return occluded_by(check_hit_mesh(M, S, ns, np, o, d), t_max);
-}
-
-// ---- one ray of a query: what a lane of ptmi_query.hip and of ptmi_query_indexed.hip does once it knows its ray ----
-enum class QueryScene { kLinear, kLinearShared, kBvh, kMesh };
-
-// `wide`: the launcher found the array 8-byte aligned (wave-uniform)
-__device__ __forceinline__ void load_ray(const float *rays, int i, bool wide, V3 &o, V3 &d)
-{
-    const float *p = rays + 6 * (size_t)i;
-    if (wide) {
-        const float2 a = reinterpret_cast<const float2 *>(p)[0], b = reinterpret_cast<const float2 *>(p)[1], c = reinterpret_cast<const float2 *>(p)[2];
-        o = mk(a.x, a.y, b.x);
-        d = mk(b.y, c.x, c.y);
-    } else {
-        o = mk(p[0], p[1], p[2]);
-        d = mk(p[3], p[4], p[5]);
-    }
-}
-
-__device__ __forceinline__ void store_hit(float *hit, int i, bool wide, V3 pos, V3 nrm)
-{
-    float *q = hit + 6 * (size_t)i;
-    if (wide) {
-        reinterpret_cast<float2 *>(q)[0] = float2{pos.x, pos.y};
-        reinterpret_cast<float2 *>(q)[1] = float2{pos.z, nrm.x};
-        reinterpret_cast<float2 *>(q)[2] = float2{nrm.y, nrm.z};
-    } else {
-        q[0] = pos.x; q[1] = pos.y; q[2] = pos.z; q[3] = nrm.x; q[4] = nrm.y; q[5] = nrm.z;
-    }
-}
-
-// flags: bit 0 the rays are 8-byte aligned, bit 1 the hit records are
-constexpr int kWideRays = 1, kWideHit = 2;
-
-// Ray i's closest hit into position i of the outputs
-template <QueryScene KIND>
-__device__ __forceinline__ void trace_ray(const SceneView &scene, const MeshView &mesh, const float *rays, int i, int flags, float *t_out, int32_t *idx_out,
-                                          float *hit_out)
-{
-    V3 o, d;
-    load_ray(rays, i, flags & kWideRays, o, d);
-    const int ns = scene.n_spheres, np = scene.n_planes;
-    HitSel h;
-    if constexpr (KIND == QueryScene::kLinear) h = check_hit(scene.packed, ns, np, o, d);
-    else if constexpr (KIND == QueryScene::kLinearShared) h = check_hit<false, SphereFold::kStash, SphereShare::kXY>(scene.packed, ns, np, o, d, nullptr, scene.share_xy);
-    else if constexpr (KIND == QueryScene::kBvh) h = check_hit_bvh(mesh.spheres, scene.packed, ns, np, o, d);
-    else h = check_hit_mesh(mesh, scene.packed, ns, np, o, d);
-    t_out[i] = h.just ? h.t : 0.0f;
-    idx_out[i] = h.just ? h.idx : -1;
-    if (hit_out) {
-        V3 pos = mk(0.0f, 0.0f, 0.0f), nrm = mk(0.0f, 0.0f, 0.0f);
-        if (h.just) {
-            if constexpr (KIND == QueryScene::kMesh) mesh_hit_record(mesh, scene.packed, ns, np, h.idx, o, d, h.t, pos, nrm);
-            else hit_record(scene.packed, ns, h.idx, o, d, h.t, pos, nrm);
-        }
-        store_hit(hit_out, i, flags & kWideHit, pos, nrm);
-    }
-}
-
-// Ray i's occlusion before t_max[i] into position i.  reach: a linear scene's SceneState.sphere_reach (occluded_linear)
-template <QueryScene KIND>
-__device__ __forceinline__ void occluded_ray(const SceneView &scene, const MeshView &mesh, float reach, const float *rays, const float *t_max, int i, int flags,
-                                             int32_t *occluded_out)
-{
-    V3 o, d;
-    load_ray(rays, i, flags & kWideRays, o, d);
-    const float limit = t_max[i];
-    const int ns = scene.n_spheres, np = scene.n_planes;
-    bool occ;
-    if constexpr (KIND == QueryScene::kLinear) occ = occluded_linear<SphereShare::kNone>(scene.packed, ns, np, 0ull, reach, o, d, limit);
-    else if constexpr (KIND == QueryScene::kLinearShared) occ = occluded_linear<SphereShare::kXY>(scene.packed, ns, np, scene.share_xy, reach, o, d, limit);
-    else if constexpr (KIND == QueryScene::kBvh) occ = occluded_bvh(mesh.spheres, scene.packed, ns, np, o, d, limit);
-    else occ = occluded_mesh(mesh, scene.packed, ns, np, o, d, limit);
-    occluded_out[i] = occ ? 1 : 0;
-}
-
-inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-// The scene kind as launch_eval_check_hit chooses it: go(the mesh kernel, the BVH one, the shared-xy one, the linear one)
-template <typename Kernel, typename F>
-hipError_t dispatch(const SceneView &scene, const BvhView *bvh, const MeshView *mesh, Kernel of_mesh, Kernel of_bvh, Kernel of_shared, Kernel of_linear, F &&go)
-{
-    if (mesh) return go(of_mesh, *mesh);
-    MeshView view{};
-    if (bvh) { view.spheres = *bvh; return go(of_bvh, view); }
-    return go(scene.share_xy ? of_shared : of_linear, view);
 }
 
 }  // namespace

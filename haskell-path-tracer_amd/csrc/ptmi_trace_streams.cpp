@@ -27,13 +27,10 @@ static int trace_streams(ptmi_ctx *c, const float *d_rays, int n, const int32_t 
     }
     if (n == 0 || n_spp <= 0 || (indexed && m == 0)) return PTMI_OK;
     PTMI_HIP(c, hipSetDevice(c->device));
-    const SceneState &s = c->scene;
-    SceneView scene;
-    scene.packed = s.packed.as<float4>(); scene.n_spheres = (int)s.rows.ns; scene.n_planes = (int)s.rows.np;
-    scene.share_xy = s.share_xy;
-    PTMI_HIP(c, launch_trace_streams(scene, s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr, d_rays, n,
-                                     indexed ? d_index : nullptr, m, n_spp, c->opt_step_cap, effective_seed_rule(c) == PTMI_SEED_FROM_RESULT, d_color, d_seed,
-                                     reinterpret_cast<unsigned long long *>(d_lost), s.has_glass ? d_work : nullptr, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    PTMI_HIP(c, launch_trace_streams(r.scene, r.bvh, r.mesh, d_rays, n, indexed ? d_index : nullptr, m, n_spp, c->opt_step_cap,
+                                     effective_seed_rule(c) == PTMI_SEED_FROM_RESULT, d_color, d_seed, reinterpret_cast<unsigned long long *>(d_lost),
+                                     c->scene.has_glass ? d_work : nullptr, c->stream));
     return PTMI_OK;
 }
 

@@ -14,13 +14,14 @@
 //     and the deeper ones in scratch memory;
 //   * the seed rule: under PTMI_SEED_FROM_RESULT every hit leaves the seed its ray carried in the ray's seed (only ever without GLASS:
 //     the entry points refuse the pair, so the lead seed and this rule never meet);
-//   * one kernel per scene kind: a linear scene staged in LDS, a linear scene too big for LDS through scalar loads, a BVH scene and a mesh
-//     scene on check_hit_bvh's LDS stack;
-//   * the index is a wave-uniform null test: lane k < m takes i = index[k] and skips an entry outside [0, n);
+//   * one kernel per scene kind (RayScene, ptmi_ray_lane_device.h, whose frame this lane stands in; kSharedXyLds is not instantiated): a
+//     linear scene staged in LDS, a linear scene too big for LDS through scalar loads, a BVH scene and a mesh scene on check_hit_bvh's LDS
+//     stack;
+//   * the index is lane_ray's wave-uniform null test: lane k < m takes i = index[k] and skips an entry outside [0, n);
 //   * what the step cap cut and what a full stack dropped go to lost[0] and lost[1], summed per wave, only when there was something.
-// Memory: rays, colour and seeds as in ptmi_paths.hip.
+// Memory: rays, colour and seeds as in ptmi_paths.hip (load_ray, load_seed and store_seed of ptmi_ray_lane_device.h).
 #define PTMI_MESH_EXACT_INLINE __forceinline__
-#include "ptmi_query_device.h"
+#include "ptmi_ray_lane_device.h"
 
 namespace ptmi {
 
@@ -29,8 +30,6 @@ namespace {
 #ifndef PTMI_TREE_WAVES
 #define PTMI_TREE_WAVES 6        // the tree walk's occupancy budget (ptmi_streams_tree.hip)
 #endif
-
-enum class StreamScene { kLinearLds, kLinearScalar, kBvh, kMesh };
 
 constexpr int kSeedFromResult = 4;     // StreamRayArgs.flags, beside kWideRays
 
@@ -47,71 +46,32 @@ struct StreamRayArgs {
     float4 *work;                // the lanes' first waiting children; null only when the scene holds no GLASS (nothing is ever pushed then)
 };
 
-template <StreamScene KIND>
+template <RayScene KIND>
 __device__ __forceinline__ void trace_streams_lane(const StreamRayArgs &a, const MeshView &uniform_mesh)
 {
-    constexpr bool LDS_SCENE = KIND == StreamScene::kLinearLds;
+    constexpr bool LDS_SCENE = staged_in_lds(KIND);
     constexpr int kEntry = 10;                               // words per start hit: position, incoming direction, throughput, primitive | steps | draws
     __shared__ uint32_t start_rec[2 * kEntry][kRenderBlock];
-    extern __shared__ float4 lds_scene[];
     const int ns = a.scene.n_spheres, np = a.scene.n_planes;
+    const float4 *S = stage_scene<KIND>(a.scene);
     if (LDS_SCENE) {
-        const int total = a.scene.total_f4();
-        for (int i = threadIdx.x; i < total; i += kRenderBlock) lds_scene[i] = a.scene.packed[i];
-        __syncthreads();
-        stage_glass_constants(lds_scene, a.scene);
+        stage_glass_constants(const_cast<float4 *>(S), a.scene);      // (S is the workgroup's own copy)
         __syncthreads();
     }
-    const float4 *S = LDS_SCENE ? lds_scene : a.scene.packed;
-    int materials = a.scene.geom_f4();
-    if constexpr (KIND == StreamScene::kBvh || KIND == StreamScene::kMesh) asm volatile("v_mov_b32 %0, %1" : "=v"(materials) : "s"(a.scene.geom_f4()));     // (per lane, as the boxes below)
-    const float4 *M = S + materials;
-    // (the hierarchies' kernels are short of scalar registers: the boxes of the admission tests are held per lane, as in ptmi_paths.hip)
-    MeshView mesh = uniform_mesh;
-    if constexpr (KIND == StreamScene::kBvh || KIND == StreamScene::kMesh) {
-        auto per_lane = [](float uniform) { float v; asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(uniform)); return v; };
-        for (int w = 0; w < 3; ++w) {
-            mesh.spheres.lo[w] = per_lane(uniform_mesh.spheres.lo[w]); mesh.spheres.hi[w] = per_lane(uniform_mesh.spheres.hi[w]);
-            if constexpr (KIND == StreamScene::kMesh) { mesh.lo[w] = per_lane(uniform_mesh.lo[w]); mesh.hi[w] = per_lane(uniform_mesh.hi[w]); }
-        }
-        // ... and the leaves' index arrays, which only ever meet a lane's own leaf
-        auto per_lane_ptr = [](const int *uniform) {
-            const uintptr_t u = reinterpret_cast<uintptr_t>(uniform);
-            uint32_t lo, hi;
-            asm volatile("v_mov_b32 %0, %1" : "=v"(lo) : "s"((uint32_t)u));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(hi) : "s"((uint32_t)(u >> 32)));
-            return reinterpret_cast<const int *>((uintptr_t)lo | ((uintptr_t)hi << 32));
-        };
-        mesh.spheres.index = per_lane_ptr(uniform_mesh.spheres.index);
-        if constexpr (KIND == StreamScene::kMesh) mesh.index = per_lane_ptr(uniform_mesh.index);
-    }
-    // the hit search: the render tree kernels'
-    auto hit = [&](V3 o, V3 d) -> HitSel {
-        if constexpr (KIND == StreamScene::kLinearLds) return check_hit<kStagedWalk>(S, ns, np, o, d);
-        else if constexpr (KIND == StreamScene::kLinearScalar) return check_hit<false>(S, ns, np, o, d);
-        else if constexpr (KIND == StreamScene::kBvh) return check_hit_bvh(mesh.spheres, S, ns, np, o, d);
-        else return check_hit_mesh(mesh, S, ns, np, o, d);
-    };
-    auto record = [&](int idx, V3 o, V3 d, float t, V3 &p, V3 &n) {
-        if constexpr (KIND == StreamScene::kMesh) mesh_hit_record(mesh, S, ns, np, idx, o, d, t, p, n);
-        else hit_record(S, ns, idx, o, d, t, p, n);
-    };
+    // (a hierarchy kernel's counts and caps are held per lane, as its boxes and here its leaves' index arrays: per_lane)
+    const float4 *M = S + (is_hierarchy(KIND) ? per_lane(a.scene.geom_f4()) : a.scene.geom_f4());
+    const MeshView mesh = per_lane_view<KIND>(uniform_mesh, std::true_type{});
+    auto record = [&](int idx, V3 o, V3 d, float t, V3 &p, V3 &n) { record_hit<KIND>(mesh, S, ns, np, idx, o, d, t, p, n); };
     auto normal_of = [&](int idx, V3 p) -> V3 {
-        if constexpr (KIND == StreamScene::kMesh) return mesh_normal_at(mesh, S, ns, np, idx, p);
+        if constexpr (is_mesh(KIND)) return mesh_normal_at(mesh, S, ns, np, idx, p);
         else return normal_at(S, ns, idx, p);
     };
     // 24 bits of primitive (PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES + PTMI_MAX_MESH_TRIANGLES <= 2^24), steps (0 or 1) at bit 24, draws (0 or 1) at bit 25
     static_assert(PTMI_MAX_BVH_SPHERES + PTMI_MAX_BVH_PLANES + PTMI_MAX_MESH_TRIANGLES <= (1 << 24), "the start record holds 24 bits of primitive");
 
-    // the lane's ray: entry k of the index, or ray k
-    const int k = blockIdx.x * kRenderBlock + threadIdx.x;
-    int i = k;
-    bool valid = k < a.n;
-    if (a.index) {
-        valid = k < a.m;
-        if (valid) { i = a.index[k]; valid = (unsigned int)i < (unsigned int)a.n; }
-    }
-    if (!valid) return;                                      // (nothing below needs the whole wave)
+    int ray;
+    if (!lane_ray(a.index, a.n, a.m, ray)) return;          // (nothing below needs the whole wave)
+    const int i = ray;
     unsigned int cut = 0, dropped = 0;
     {
         V3 origin, primary;
@@ -123,20 +83,11 @@ __device__ __forceinline__ void trace_streams_lane(const StreamRayArgs &a, const
             const float *c = a.color + 3 * (size_t)i;
             const uint32_t *seed_p = a.seed + 4 * (size_t)i;
             acc = mk(c[0], c[1], c[2]);
-            if ((reinterpret_cast<uintptr_t>(seed_p) & 15u) == 0) {
-                const uint4 w = *reinterpret_cast<const uint4 *>(seed_p);
-                pixel_seed.a = w.x; pixel_seed.b = w.y; pixel_seed.c = w.z; pixel_seed.counter = w.w;
-            } else {
-                pixel_seed.a = seed_p[0]; pixel_seed.b = seed_p[1]; pixel_seed.c = seed_p[2]; pixel_seed.counter = seed_p[3];
-            }
+            load_seed(seed_p, seed_is_wide(seed_p), pixel_seed);
         }
-        int n_spp = a.n_spp, cap_i = a.step_cap, from_result = a.flags & kSeedFromResult;
-        if constexpr (KIND == StreamScene::kBvh || KIND == StreamScene::kMesh) {      // (per lane, as the boxes)
-            asm volatile("v_mov_b32 %0, %1" : "=v"(n_spp) : "s"(a.n_spp));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(cap_i) : "s"(a.step_cap));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(from_result) : "s"(a.flags & kSeedFromResult));
-        }
-        const unsigned int step_cap = (unsigned int)cap_i;
+        const int n_spp = is_hierarchy(KIND) ? per_lane(a.n_spp) : a.n_spp;
+        const unsigned int step_cap = (unsigned int)(is_hierarchy(KIND) ? per_lane(a.step_cap) : a.step_cap);
+        const int from_result = is_hierarchy(KIND) ? per_lane(a.flags & kSeedFromResult) : a.flags & kSeedFromResult;
         // the seed rule as a mask of all ones (PTMI_SEED_FROM_RESULT) or none: the seed a hit's ray carried is taken by bit selection, so that
         // no comparison's lane mask lives in scalar registers across the loop
         const uint32_t take = 0u - ((uint32_t)from_result / (uint32_t)kSeedFromResult);
@@ -296,7 +247,8 @@ __device__ __forceinline__ void trace_streams_lane(const StreamRayArgs &a, const
                     else state = kHasRay;
                 }
                 if (state >= kHasRay) {
-                    const HitSel h = hit(pos, d);
+                    // the hit search: the render tree kernels'
+                    const HitSel h = closest_hit<KIND, kStagedWalk, SphereFold::kStash, SphereShare::kNone>(mesh, S, ns, np, 0ull, pos, d);
                     V3 hp = pos, hn = normal;
                     if (h.just) record(h.idx, pos, d, h.t, hp, hn);
                     if (state == kHasRay) {
@@ -358,11 +310,7 @@ __device__ __forceinline__ void trace_streams_lane(const StreamRayArgs &a, const
         float *c = a.color + 3 * (size_t)i;
         uint32_t *seed_p = a.seed + 4 * (size_t)i;
         c[0] = acc.x; c[1] = acc.y; c[2] = acc.z;
-        if ((reinterpret_cast<uintptr_t>(seed_p) & 15u) == 0) {
-            *reinterpret_cast<uint4 *>(seed_p) = uint4{pixel_seed.a, pixel_seed.b, pixel_seed.c, pixel_seed.counter};
-        } else {
-            seed_p[0] = pixel_seed.a; seed_p[1] = pixel_seed.b; seed_p[2] = pixel_seed.c; seed_p[3] = pixel_seed.counter;
-        }
+        store_seed(seed_p, seed_is_wide(seed_p), pixel_seed);
     }
     if (__any((cut | dropped) != 0u)) {                               // rare: one add per word and wave, summed over the lanes that lost something
         unsigned long long n_cut = 0, n_dropped = 0;
@@ -383,10 +331,10 @@ __device__ __forceinline__ void trace_streams_lane(const StreamRayArgs &a, const
     {                                                                                                                                \
         trace_streams_lane<KIND>(a, mesh);                                                                                           \
     }
-PTMI_STREAM_RAYS_KERNEL(linear_lds, StreamScene::kLinearLds, PTMI_TREE_WAVES)
-PTMI_STREAM_RAYS_KERNEL(linear_scalar, StreamScene::kLinearScalar, PTMI_TREE_WAVES)
-PTMI_STREAM_RAYS_KERNEL(bvh, StreamScene::kBvh, PTMI_BVH_WAVES)
-PTMI_STREAM_RAYS_KERNEL(mesh, StreamScene::kMesh, PTMI_BVH_WAVES)
+PTMI_STREAM_RAYS_KERNEL(linear_lds, RayScene::kLinearLds, PTMI_TREE_WAVES)
+PTMI_STREAM_RAYS_KERNEL(linear_scalar, RayScene::kLinearScalar, PTMI_TREE_WAVES)
+PTMI_STREAM_RAYS_KERNEL(bvh, RayScene::kBvh, PTMI_BVH_WAVES)
+PTMI_STREAM_RAYS_KERNEL(mesh, RayScene::kMesh, PTMI_BVH_WAVES)
 #undef PTMI_STREAM_RAYS_KERNEL
 
 }  // namespace
@@ -409,14 +357,9 @@ hipError_t launch_trace_streams(SceneView scene, const BvhView *bvh, const MeshV
     a.n_spp = n_spp; a.step_cap = step_cap;
     a.flags = (aligned8(rays) ? kWideRays : 0) | (seed_from_result ? kSeedFromResult : 0);
     a.color = color; a.seed = seed; a.lost = lost; a.work = static_cast<float4 *>(work);
-    const dim3 grid(blocks_for(lanes, kRenderBlock)), block(kRenderBlock);
-    if (mesh) return launch(trace_streams_mesh_kernel, grid, block, 0, stream, a, *mesh);
-    MeshView view{};
-    if (bvh) { view.spheres = *bvh; return launch(trace_streams_bvh_kernel, grid, block, 0, stream, a, view); }
-    // a scene so big that staging it per wave would cost more occupancy than scalar loads cost speed is read through scalar loads (scene_fits_lds)
-    const size_t lds = (size_t)scene.total_f4() * sizeof(float4);
-    if (lds > kMaxSceneLds) return launch(trace_streams_linear_scalar_kernel, grid, block, 0, stream, a, view);
-    return launch(trace_streams_linear_lds_kernel, grid, block, lds, stream, a, view);
+    // (no kernel of its own for shared-xy runs: the tree walk's check_hit does not follow them)
+    return launch_by_scene(scene, bvh, mesh, trace_streams_mesh_kernel, trace_streams_bvh_kernel, trace_streams_linear_scalar_kernel, trace_streams_linear_lds_kernel,
+                           trace_streams_linear_lds_kernel, lanes, stream, a);
 }
 
 }  // namespace ptmi
