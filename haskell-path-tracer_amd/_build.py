@@ -24,7 +24,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libptmi.so")
 ABLATIONS_LIB = os.path.join(HERE, "libptmi_ablations.so")   # the same library with the ablation kernels of DESIGN.md 5.2 (tests, measurements)
 OBJ_ROOT = os.path.join(ROOT, "build", "obj")
-HOST_SOURCES = ["ptmi_api.cpp", "ptmi_chain.cpp", "ptmi_stream_call.cpp", "ptmi_scene.cpp", "ptmi_stage.cpp", "ptmi_group.cpp", "ptmi_bvh.cpp", "ptmi_mesh.cpp", "ptmi_ray_order.cpp", "ptmi_bounce.cpp", "ptmi_trace_streams.cpp"]
+HOST_SOURCES = ["ptmi_api.cpp", "ptmi_order.cpp", "ptmi_chain.cpp", "ptmi_stream_call.cpp", "ptmi_scene.cpp", "ptmi_stage.cpp", "ptmi_group.cpp", "ptmi_bvh.cpp", "ptmi_mesh.cpp", "ptmi_ray_order.cpp", "ptmi_bounce.cpp", "ptmi_trace_streams.cpp"]
 BUILD_ID_UNIT = "ptmi_build_id.cpp"                          # ptmi_build_id(): compiled at every link with -DPTMI_BUILD_ID=<the code the library holds>
 BUILD_ID_MARKER = b"PTMI_BUILD_ID="                          # ... behind this marker in the binary, so that the file can be asked without loading it
 SOURCE_HASH_MARKER = b"PTMI_SOURCE_HASH="                    # ... and the hash of the source TEXT it was linked from (staleness only, see source_hash)

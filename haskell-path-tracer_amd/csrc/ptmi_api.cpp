@@ -1,5 +1,6 @@
-// ptmi_api.cpp -- the C ABI of include/ptmi.h: context, device planes, options, launches and the queries (the scene's calls are
-// ptmi_scene.cpp's, the chained closure's ptmi_chain.cpp's, the stream form of Streams is ptmi_stream_call.cpp; ptmi_ctx.h is what they share).
+// ptmi_api.cpp -- the C ABI of include/ptmi.h: context, device planes, the option table, launches, their statistics (RenderStats) and the
+// queries (the scene's calls are ptmi_scene.cpp's, the chained closure's ptmi_chain.cpp's, the stream form of Streams is ptmi_stream_call.cpp,
+// the cost-ordered dispatch ptmi_order.cpp; ptmi_ctx.h is what they share).
 // Compiled with hipcc together with the kernel units (ptmi_*.hip) into libptmi.so.  There is no CPU
 // fallback here: without a HIP device ptmi_create fails with PTMI_ENODEVICE.
 #include "ptmi_ctx.h"
@@ -91,18 +92,27 @@ int ptmi::effective_seed_rule(const ptmi_ctx *c)
     return c->scene.has_glass ? PTMI_SEED_KEEP_ACCUMULATOR : PTMI_SEED_FROM_RESULT;
 }
 
+SceneView ptmi::scene_view(const SceneState &s)
+{
+    SceneView v;
+    v.packed = s.packed.as<float4>(); v.n_spheres = (int)s.rows.ns; v.n_planes = (int)s.rows.np;
+    v.share_xy = s.share_xy;
+    return v;
+}
+
 RayCallScene ptmi::ray_call_scene(const ptmi_ctx *c)
 {
     const SceneState &s = c->scene;
-    RayCallScene r;
-    r.scene.packed = s.packed.as<float4>(); r.scene.n_spheres = (int)s.rows.ns; r.scene.n_planes = (int)s.rows.np;
-    r.scene.share_xy = s.share_xy;
-    r.bvh = s.kind == SceneKind::Bvh ? &s.bvh : nullptr;
-    r.mesh = s.kind == SceneKind::Mesh ? &s.mesh : nullptr;
-    return r;
+    return {scene_view(s), s.kind == SceneKind::Bvh ? &s.bvh : nullptr, s.kind == SceneKind::Mesh ? &s.mesh : nullptr};
 }
 
 namespace {
+
+// A refusal that a BVH scene and a mesh scene share but for their names: "a BVH" / "a mesh", then `rest`
+int refuse_kind(ptmi_ctx *c, const char *rest)
+{
+    return fail(c, PTMI_EINVAL, std::string(c->scene.kind == SceneKind::Bvh ? "a BVH" : "a mesh") + rest);
+}
 
 // PTMI_OPT_STREAMS_FORM resolved: does `render Streams` run in its stream ("wavefront") form?  AUTO: only where it pays and costs nothing that
 // was promised -- a scene with GLASS (no reference semantics, no defined addition order in Accelerate's permute either) on ONE PART of a
@@ -185,101 +195,101 @@ PrimaryUniforms make_uniforms(const ptmi_camera &cam, int width, int height)
     return u;
 }
 
-constexpr size_t kLiveBytes = (size_t)kStatShards * kStatStride * sizeof(unsigned long long);     // sharded statistics (ptmi_kernels.h)
+}  // namespace
 
-// The schedule of the cost-ordered dispatch: `launches` = launches made so far with one (camera, scene, shape, limit, algorithm).
-// The order is REBUILT from the recorded costs before launch 1, 2, 4, 8, ... -- and never again once the limit is reached: the state stops
-// there, it is a power of two itself, and a rebuild bumps the order's generation, which would make the stream form re-run its primary kernel
-// on every later call of a standing camera.  A launch RECORDS its costs only if the NEXT launch rebuilds -- launch 0, 1, 3, 7, 15, ... (the
-// sums stay far from 2^32) -- since round 5: a recorded cost is an atomic per wave, or per item in the stream form, on words that all XCDs share
-// (32 bytes of write traffic each, tools/traffic_terms.py), and between two rebuilds nobody reads them; every rebuild still sees one more
-// launch than the one before it, and a standing camera's steady state records nothing.
-int order_schedule(int launches, int stream_form, int *rebuild, int *record)
+// ---- the statistics (RenderStats, ptmi_ctx.h)
+hipError_t RenderStats::create(hipStream_t stream, const char **failed_call)
 {
-    const int limit = stream_form ? (1 << 11) : (1 << 20);
-    const bool below = launches >= 0 && launches < limit;
-    if (rebuild) *rebuild = (below && launches > 0 && (launches & (launches - 1)) == 0) ? 1 : 0;
-    if (record) *record = (below && launches + 1 < limit && ((launches + 1) & launches) == 0) ? 1 : 0;
-    return below ? launches + 1 : limit;
+    hipError_t e;
+    *failed_call = "hipEventCreate";
+    if ((e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) return e;
+    *failed_call = "hipMalloc";
+    for (int i : {Live, Work, Iters, StreamCounters})
+        if ((e = allocate(block[i], kBytes[i])) != hipSuccess) return e;
+    *failed_call = "hipMemsetAsync";      // stream-ordered fills: the context's stream is non-blocking, so a NULL-stream hipMemset would race with it
+    for (int i : {StreamCounters, Live, Work, Iters})
+        if ((e = hipMemsetAsync(block[i].p, 0, kBytes[i], stream)) != hipSuccess) return e;
+    return hipSuccess;
 }
 
-}  // namespace
+int RenderStats::reset(ptmi_ctx *c)
+{
+    for (int i : {Live, Iters, Work, StreamCounters}) PTMI_HIP(c, hipMemsetAsync(block[i].p, 0, kBytes[i], c->stream));
+    nominal = 0; samples = 0;
+    return PTMI_OK;
+}
+
+int RenderStats::read(ptmi_ctx *c, ptmi_stats *out)
+{
+    unsigned long long live = 0, sc[kScWords] = {0, 0, 0, 0}; unsigned int iters = 0;
+    std::vector<unsigned long long> live_shards((size_t)kStatShards * kStatStride);     // the sharded statistics: sum / maximum over the shards
+    std::vector<unsigned int> iter_shards((size_t)kStatShards * 2 * kStatStride);
+    const std::pair<void *, int> reads[3] = {{live_shards.data(), Live}, {sc, StreamCounters}, {iter_shards.data(), Iters}};
+    for (const auto &[host, i] : reads) PTMI_HIP(c, hipMemcpyAsync(host, block[i].p, kBytes[i], hipMemcpyDeviceToHost, c->stream));
+    PTMI_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < kStatShards; ++k) {
+        live += live_shards[(size_t)k * kStatStride];
+        iters = std::max(iters, iter_shards[(size_t)k * 2 * kStatStride]);
+    }
+    const StreamFormState::Totals &form = c->stream_form.totals;
+    out->live_bounces = live + form.live_host; out->nominal_bounces = nominal; out->samples = samples;
+    out->stream_iterations = iters;
+    out->stream_rays_dropped = form.rays_dropped + sc[kScDropped];
+    out->stream_rays_truncated = form.rays_truncated + sc[kScTruncated];
+    out->stream_rays_spilled = form.rays_spilled;
+    out->stream_rays_overflowed = form.rays_overflowed;
+    out->last_render_ms = 0.0f;
+    if (timing && ev_valid) PTMI_HIP(c, hipEventElapsedTime(&out->last_render_ms, ev0, ev1));
+    return PTMI_OK;
+}
+
+int RenderStats::launches_begin(ptmi_ctx *c, RenderArgs &a)
+{
+    a.live_counter = block[Live].as<unsigned long long>(); a.work_counter = block[Work].as<unsigned int>(); a.stream_iterations = block[Iters].as<unsigned int>();
+    a.stream_counters = block[StreamCounters].as<unsigned long long>();
+    if (timing) PTMI_HIP(c, hipEventRecord(ev0, c->stream));
+    return PTMI_OK;
+}
+int RenderStats::launches_end(ptmi_ctx *c, uint64_t samples_made, uint64_t bounces_nominal)
+{
+    if (timing) { PTMI_HIP(c, hipEventRecord(ev1, c->stream)); ev_valid = true; }
+    samples += samples_made; nominal += bounces_nominal;
+    return PTMI_OK;
+}
 
 int ptmi::launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp)
 {
     const auto &[planes, width, height, rows_local, stripe_rows, n_parts, part, sx, sy] = target;
     RenderArgs a{};
     a.cam = make_uniforms(*camera, width, height);
-    a.scene.packed = c->scene.packed.as<float4>(); a.scene.n_spheres = (int)c->scene.rows.ns; a.scene.n_planes = (int)c->scene.rows.np;
-    a.scene.share_xy = c->scene.share_xy;
+    a.scene = scene_view(c->scene);
     a.planes = planes;
     a.screen_x = sx; a.screen_y = sy;
     a.width = width; a.height = height; a.rows_local = rows_local;
     a.stripe_rows = stripe_rows; a.n_parts = n_parts; a.part = part;
     a.bounce_limit = bounce_limit; a.n_spp = n_spp;
     a.cus = c->cus;
-    a.live_counter = c->d_live.as<unsigned long long>(); a.work_counter = c->d_work.as<unsigned int>(); a.stream_iterations = c->d_iters.as<unsigned int>();
     a.stream_step_cap = c->opt_step_cap; a.seed_from_result = effective_seed_rule(c) == PTMI_SEED_FROM_RESULT;
-    a.stream_counters = c->d_stream_counters.as<unsigned long long>();
     const bool stream_form = uses_stream_form(c, algorithm, n_parts, n_spp);
-    // Cost-ordered dispatch (ptmi_device.h: lane_pixel): launches with one (camera, scene, shape, limit, algorithm)
-    // record what every quad of tiles costs; later launches with the same key dispatch the most expensive quads first
-    // (sorted on the device).  Everything is enqueued on the stream; results do not depend on it.
-    const bool per_pixel_kernel = !stream_form;
-    int next_order_state = c->order_state;
-    // (the stream form orders its start-hit list the same way, under a key of its own; its items record their costs)
+    // Which launches take the cost-ordered dispatch (DispatchOrder, ptmi_order.cpp): the tiled per-pixel kernels', and the stream form's,
+    // which orders its start-hit list the same way
 #ifdef PTMI_STREAM_NO_ORDER
     const bool stream_order = false;
 #else
     const bool stream_order = quad_positions(width, rows_local) > 0 && !sx;
 #endif
-    if (stream_form ? stream_order : uses_quad_order(a, algorithm == PTMI_INLINE, c->variant)) {
-        const unsigned int n_quads = quad_positions(width, rows_local);
-        const size_t quad_bytes = n_quads * sizeof(unsigned int);
-        DeviceBlock *quads[3] = {&c->d_quad_cost, &c->d_quad_order, &c->d_quad_class};
-        if (std::any_of(quads, quads + 3, [&](const DeviceBlock *q) { return q->bytes < quad_bytes; })) {
-            c->order_state = 0; ++c->order_generation;
-            for (DeviceBlock *q : quads)
-                if (int rc = grow(c, *q, quad_bytes, "the dispatch order")) return rc;
-        }
-        ptmi_ctx::OrderKey key{};
-        key.cam = *camera; key.scene_version = c->scene.version;
-        const int dims[8] = {width, height, rows_local, stripe_rows, n_parts, part, bounce_limit, stream_form ? 2 : algorithm};
-        std::memcpy(key.dims, dims, sizeof dims);
-        if (std::memcmp(&key, &c->order_key, sizeof key) != 0) { c->order_key = key; c->order_state = 0; ++c->order_generation; }
-        // order_state counts the launches made with this key.  The launches before a rebuild add their costs (a 1-spp launch says little
-        // on its own: the compat entry renders one sample per call); the order is rebuilt before launch 1, 2, 4, 8, ...
-        const int launches = c->order_state;
-        int rebuild = 0, record = 0;
-        const int state_after = order_schedule(launches, stream_form ? 1 : 0, &rebuild, &record);
-        if (int rc = grow(c, c->d_tail_start, 64, "the tail's start")) return rc;
-        if (launches == 0) {
-            PTMI_HIP(c, hipMemsetAsync(c->d_quad_cost.p, 0, quad_bytes, c->stream));
-            PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_tail_start.p), (int)n_quads, 1, c->stream));   // no tail yet
-        } else if (rebuild) {
-            // (the stream form: the order kernel also says where the order's cheap end begins -- render_streams_wavefront.  How much of the
-            // recorded cost that end may hold: 15 % where a lane sees four pixels or more, 40 % where it sees fewer -- 1280x720 / 64 spp: 2.34 ms
-            // with 15 %, 2.16 with 40 %, chain kernel 1.96; 1080p: 4.24 / 4.21.)
-            const unsigned long long lanes_full = 64ull * (unsigned long long)(c->cus > 0 ? c->cus : 256) * 4ull * (unsigned long long)streams_pixels_waves();
-            const unsigned int tail_permille = c->opt_tail_permille >= 0 ? (unsigned int)c->opt_tail_permille
-                                             : ((unsigned long long)width * (unsigned long long)rows_local < 4ull * lanes_full ? 400u : 150u);
-            PTMI_HIP(c, launch_quad_order(c->d_quad_cost.as<unsigned int>(), c->d_quad_order.as<unsigned int>(), c->d_quad_class.as<unsigned int>(), n_quads,
-                                          stream_form ? c->d_tail_start.as<unsigned int>() : nullptr, tail_permille, c->stream));
-            ++c->order_generation;
-        }
-        if (launches > 0) a.quad_order = c->d_quad_order.as<unsigned int>();
-        if (record) a.quad_cost = c->d_quad_cost.as<unsigned int>();
-        next_order_state = state_after;                        // (every launch counts, whether or not it records)
-    }
-    if (per_pixel_kernel) {
+    const bool ordered = stream_form ? stream_order : uses_quad_order(a, algorithm == PTMI_INLINE, c->variant);
+    if (ordered)
+        if (int rc = c->order.before_launches(c, *camera, c->scene.version, target, bounce_limit, algorithm, stream_form, a)) return rc;
+    if (!stream_form) {
         // one word per tile workgroup for the sample chunks of the tiled per-pixel kernels (ptmi_device.h: enter_sample_chunk)
         const unsigned int need = ((unsigned int)(((width + 7) / 8) * ((rows_local + 7) / 8)) + 31u) & ~31u;
         if (int rc = grow(c, c->d_chunk_done, ((size_t)need + 32) * sizeof(unsigned int), "the sample chunks")) return rc;     // + the ticket counter's line
         a.chunk_done = c->d_chunk_done.as<unsigned int>(); a.chunk_capacity = c->chunk_capacity();
         a.spp_chunks = sx ? 1 : c->opt_spp_chunks;
     }
-    if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev0, c->stream)); }
-    const BvhView *bvh = c->scene.kind == SceneKind::Bvh ? &c->scene.bvh : nullptr;    // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
+    if (int rc = c->stats.launches_begin(c, a)) return rc;
+    const BvhView *bvh = ray_call_scene(c).bvh;            // the per-pixel kernels' BVH instantiations (check_render_args refused the rest)
     if (algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED) {
         PTMI_HIP(c, (hipError_t)ptmi_contracted_launch_inline(&a, c->variant == kVariantStreamForm ? kVariantAuto : c->variant, c->stream));
     } else if (algorithm == PTMI_INLINE && c->scene.kind == SceneKind::Mesh) {
@@ -300,12 +310,10 @@ int ptmi::launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_came
     } else {
         PTMI_HIP(c, launch_render_streams(a, bvh, c->variant, c->stream));
     }
-    if (c->timing) { PTMI_HIP(c, hipEventRecord(c->ev1, c->stream)); c->ev_valid = true; }
-    c->order_state = next_order_state;
-    const uint64_t px = (uint64_t)rows_local * (uint64_t)width;
-    c->samples += px * (uint64_t)(n_spp > 0 ? n_spp : 0);
-    if (algorithm == PTMI_INLINE)                          // Streams ignores the limit (Trace.hs:166-170): no nominal count
-        c->nominal += px * (uint64_t)(n_spp > 0 ? n_spp : 0) * (uint64_t)(bounce_limit > 0 ? bounce_limit : 0);
+    const uint64_t samples = (uint64_t)rows_local * (uint64_t)width * (uint64_t)(n_spp > 0 ? n_spp : 0);
+    // (Streams ignores the limit, Trace.hs:166-170: no nominal count)
+    if (int rc = c->stats.launches_end(c, samples, algorithm == PTMI_INLINE ? samples * (uint64_t)(bounce_limit > 0 ? bounce_limit : 0) : 0)) return rc;
+    if (ordered) c->order.launches_went_out();
     return PTMI_OK;
 }
 
@@ -321,10 +329,8 @@ int ptmi::check_render_args(ptmi_ctx *c, const ptmi_camera *camera, int algorith
         return fail(c, PTMI_EINVAL, "the scene holds a GLASS material: render Inline cannot split rays, use PTMI_STREAMS");
     if (algorithm == PTMI_STREAMS && c->scene.has_glass && c->opt_seed_rule == PTMI_SEED_FROM_RESULT)
         return fail(c, PTMI_EINVAL, "PTMI_SEED_FROM_RESULT is undefined when rays split (GLASS): several results race for one pixel's seed");
-    if (c->scene.kind == SceneKind::Bvh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
-        return fail(c, PTMI_EINVAL, "a BVH scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
-    if (c->scene.kind == SceneKind::Mesh && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
-        return fail(c, PTMI_EINVAL, "a mesh scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
+    if (c->scene.hierarchical() && algorithm == PTMI_INLINE && c->opt_arithmetic == PTMI_ARITH_CONTRACTED)
+        return refuse_kind(c, " scene has no contracted-arithmetic kernel (PTMI_OPT_ARITHMETIC)");
     return PTMI_OK;
 }
 
@@ -334,6 +340,54 @@ void ptmi::context_size(const ptmi_ctx *cc, int *width, int *height)
     std::lock_guard<std::mutex> lock(c->mu);
     *width = c->width; *height = c->height;
 }
+
+namespace {
+
+// ---- the options: one row each.  A value is accepted within [lo, hi] unless `but` says otherwise; it is the context's `member`, set and
+// read as it is -- or through the row's hooks, where setting does more than that or the value lives elsewhere.
+struct Option {
+    int id;
+    int ptmi_ctx::*member;
+    int64_t lo, hi;
+    const char *refusal;
+    bool (*but)(int64_t value);                 // within [lo, hi] and refused all the same
+    int (*set)(ptmi_ctx *c, int value);         // instead of the plain store (the value is an accepted one)
+    int64_t (*get)(ptmi_ctx *c);                // instead of the plain read
+};
+const Option kOptions[] = {
+    {PTMI_OPT_STREAMS_SEED_RULE, &ptmi_ctx::opt_seed_rule, PTMI_SEED_KEEP_ACCUMULATOR, PTMI_SEED_AUTO, "unknown seed rule"},
+    {PTMI_OPT_STREAM_STEP_CAP, &ptmi_ctx::opt_step_cap, 1, 1 << 30, "step cap must be in [1, 2^30]"},
+    {PTMI_OPT_STREAM_CAPACITY, &ptmi_ctx::opt_capacity, 1, 64, "stream capacity must be in [1, 64] rays per pixel-sample", nullptr,
+     [](ptmi_ctx *c, int value) { c->opt_capacity = value; return c->stream_form.forget_streams(c); },
+     [](ptmi_ctx *c) { return (int64_t)c->stream_form.rays_per_pixel(c->opt_capacity); }},      // (what an earlier call grew the streams to counts)
+    {PTMI_OPT_STREAMS_FORM, &ptmi_ctx::opt_form, PTMI_FORM_AUTO, PTMI_FORM_PIXEL, "unknown Streams form", nullptr,
+     [](ptmi_ctx *c, int value) {
+         if (c->scene.hierarchical() && value == PTMI_FORM_STREAM) return refuse_kind(c, " scene has no stream form (PTMI_FORM_STREAM)");
+         return c->opt_form = value, (int)PTMI_OK;
+     }},
+    {PTMI_OPT_STREAM_BATCH, &ptmi_ctx::opt_batch, 0, 64, "stream batch must be in [0, 64] samples"},
+    {PTMI_OPT_SPP_CHUNKS, &ptmi_ctx::opt_spp_chunks, 0, 64, "sample chunks must be in [0, 64]"},
+    {PTMI_OPT_ARITHMETIC, &ptmi_ctx::opt_arithmetic, PTMI_ARITH_EXACT, PTMI_ARITH_CONTRACTED, "unknown arithmetic mode"},
+    {PTMI_OPT_STREAM_TAIL, nullptr, -1, 1000, "stream tail must be -1 (automatic) or thousandths in [0, 1000]", nullptr,      // the dispatch order's
+     [](ptmi_ctx *c, int value) { c->order.tail_option() = value; return (int)PTMI_OK; }, [](ptmi_ctx *c) { return (int64_t)c->order.tail_option(); }},
+    {PTMI_OPT_ORDERED_PASSES, &ptmi_ctx::opt_ordered_passes, 0, 64, "ordered passes must be 0 (automatic), 1 (off) or k in [2, 64]"},
+    {PTMI_OPT_GLASS_BATCH, &ptmi_ctx::opt_glass_batch, 0, 64, "glass batch must be 0 (automatic), 1 (off) or k in [2, 64] lanes"},
+    {PTMI_OPT_STREAM_GRADED, &ptmi_ctx::opt_graded, 0, 1, "graded passes are on (1) or off (0)"},
+    {PTMI_OPT_SNAPSHOT_BUDGET_MB, &ptmi_ctx::opt_snapshot_mb, 0, 1 << 20, "snapshot budget must be 0 (automatic) or megabytes in [1, 2^20]"},
+    {PTMI_OPT_STREAM_PASS_GROUPS, &ptmi_ctx::opt_pass_groups, 0, 164,
+     "pass groups must be 0 (automatic), 1 (every pass on its own), k in [2, 64] or 100 + g, g in [2, 64]", [](int64_t value) { return value > 64 && value < 102; }},
+    {PTMI_OPT_CHAIN_SLOTS, &ptmi_ctx::opt_chain_slots, 0, 4096, "chain slots must be 0 (automatic) or in [2, 4096]", [](int64_t value) { return value == 1; }},
+    {PTMI_OPT_PASS_HANDOFF, &ptmi_ctx::opt_pass_handoff, PTMI_HANDOFF_FENCED, PTMI_HANDOFF_FENCE_FREE, "unknown pass hand-off"},
+    {PTMI_OPT_BVH_DEVICE_BUILD, &ptmi_ctx::opt_bvh_build, PTMI_BVH_BUILD_EQUAL_COUNT, PTMI_BVH_BUILD_SPATIAL, "unknown device build of the sphere hierarchy"},
+};
+const Option *find_option(int id)
+{
+    for (const Option &o : kOptions)
+        if (o.id == id) return &o;
+    return nullptr;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -392,18 +446,9 @@ int ptmi_create(ptmi_ctx **out, int device)
     }
     if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
     c->stream = c->own_stream;
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipEventCreateWithFlags(&c->ev_snap, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = allocate(c->d_live, kLiveBytes)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = allocate(c->d_work, kWorkWords * sizeof(unsigned int))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = allocate(c->d_iters, kItersBytes)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = allocate(c->d_stream_counters, kScWords * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemsetAsync(c->d_stream_counters.p, 0, kScWords * sizeof(unsigned long long), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    // stream-ordered fills: the context's stream is non-blocking, so a NULL-stream hipMemset would race with it
-    if ((e = hipMemsetAsync(c->d_live.p, 0, kLiveBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    if ((e = hipMemsetAsync(c->d_work.p, 0, kWorkWords * sizeof(unsigned int), c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    if ((e = hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    const char *failed_call = nullptr;
+    if ((e = c->stats.create(c->stream, &failed_call)) != hipSuccess) return bail(e, failed_call);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
     *out = c;
     return PTMI_OK;
@@ -416,8 +461,8 @@ void ptmi_destroy(ptmi_ctx *c)
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     c->each_block([](DeviceBlock &b) { release(b); });
     c->stream_form.destroy_handles();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->stats.ev0) (void)hipEventDestroy(c->stats.ev0);
+    if (c->stats.ev1) (void)hipEventDestroy(c->stats.ev1);
     if (c->ev_snap) (void)hipEventDestroy(c->ev_snap);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     (void)hipGetLastError();                                 // whatever failed above was ignored on purpose: it is nobody else's to find
@@ -515,7 +560,7 @@ int ptmi_set_stream(ptmi_ctx *c, void *hip_stream)
     PTMI_HIP(c, hipSetDevice(c->device));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
-    c->ev_valid = false;
+    c->stats.ev_valid = false;
     return PTMI_OK;
 }
 
@@ -523,8 +568,8 @@ int ptmi_set_timing(ptmi_ctx *c, int enabled)
 {
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
-    c->timing = enabled != 0;
-    c->ev_valid = false;
+    c->stats.timing = enabled != 0;
+    c->stats.ev_valid = false;
     return PTMI_OK;
 }
 
@@ -534,75 +579,21 @@ int ptmi_set_variant(ptmi_ctx *c, int variant)
     std::lock_guard<std::mutex> lock(c->mu);
     if (variant < 0 || variant >= kVariantCount) return fail(c, PTMI_EINVAL, "unknown variant");
     if (!variant_available(variant)) return fail(c, PTMI_EINVAL, "this variant is an ablation kernel: build libptmi with -DPTMI_ABLATIONS");
-    if (c->scene.kind == SceneKind::Bvh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a BVH scene renders through the default kernels only (variant 0)");
-    if (c->scene.kind == SceneKind::Mesh && variant != kVariantAuto) return fail(c, PTMI_EINVAL, "a mesh scene renders through the default kernels only (variant 0)");
+    if (c->scene.hierarchical() && variant != kVariantAuto) return refuse_kind(c, " scene renders through the default kernels only (variant 0)");
     c->variant = variant;
     return PTMI_OK;
-}
-
-int ptmi_order_schedule(int launches, int stream_form, int *rebuild, int *record)
-{
-    return order_schedule(launches, stream_form, rebuild, record);
 }
 
 int ptmi_set_option(ptmi_ctx *c, int option, int64_t value)
 {
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
-    switch (option) {
-    case PTMI_OPT_STREAMS_SEED_RULE:
-        if (value != PTMI_SEED_KEEP_ACCUMULATOR && value != PTMI_SEED_FROM_RESULT && value != PTMI_SEED_AUTO) return fail(c, PTMI_EINVAL, "unknown seed rule");
-        c->opt_seed_rule = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_STEP_CAP:
-        if (value < 1 || value > (1 << 30)) return fail(c, PTMI_EINVAL, "step cap must be in [1, 2^30]");
-        c->opt_step_cap = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_CAPACITY:
-        if (value < 1 || value > 64) return fail(c, PTMI_EINVAL, "stream capacity must be in [1, 64] rays per pixel-sample");
-        c->opt_capacity = (int)value;
-        return c->stream_form.forget_streams(c);
-    case PTMI_OPT_STREAMS_FORM:
-        if (value != PTMI_FORM_AUTO && value != PTMI_FORM_STREAM && value != PTMI_FORM_PIXEL) return fail(c, PTMI_EINVAL, "unknown Streams form");
-        if (c->scene.kind == SceneKind::Bvh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a BVH scene has no stream form (PTMI_FORM_STREAM)");
-        if (c->scene.kind == SceneKind::Mesh && value == PTMI_FORM_STREAM) return fail(c, PTMI_EINVAL, "a mesh scene has no stream form (PTMI_FORM_STREAM)");
-        c->opt_form = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_BATCH:
-        if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "stream batch must be in [0, 64] samples");
-        c->opt_batch = (int)value; return PTMI_OK;
-    case PTMI_OPT_SPP_CHUNKS:
-        if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "sample chunks must be in [0, 64]");
-        c->opt_spp_chunks = (int)value; return PTMI_OK;
-    case PTMI_OPT_ARITHMETIC:
-        if (value != PTMI_ARITH_EXACT && value != PTMI_ARITH_CONTRACTED) return fail(c, PTMI_EINVAL, "unknown arithmetic mode");
-        c->opt_arithmetic = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_TAIL:
-        if (value < -1 || value > 1000) return fail(c, PTMI_EINVAL, "stream tail must be -1 (automatic) or thousandths in [0, 1000]");
-        c->opt_tail_permille = (int)value; return PTMI_OK;
-    case PTMI_OPT_ORDERED_PASSES:
-        if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "ordered passes must be 0 (automatic), 1 (off) or k in [2, 64]");
-        c->opt_ordered_passes = (int)value; return PTMI_OK;
-    case PTMI_OPT_GLASS_BATCH:
-        if (value < 0 || value > 64) return fail(c, PTMI_EINVAL, "glass batch must be 0 (automatic), 1 (off) or k in [2, 64] lanes");
-        c->opt_glass_batch = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_GRADED:
-        if (value != 0 && value != 1) return fail(c, PTMI_EINVAL, "graded passes are on (1) or off (0)");
-        c->opt_graded = (int)value; return PTMI_OK;
-    case PTMI_OPT_SNAPSHOT_BUDGET_MB:
-        if (value < 0 || value > (1 << 20)) return fail(c, PTMI_EINVAL, "snapshot budget must be 0 (automatic) or megabytes in [1, 2^20]");
-        c->opt_snapshot_mb = (int)value; return PTMI_OK;
-    case PTMI_OPT_STREAM_PASS_GROUPS:
-        if (value < 0 || value > 164 || (value > 64 && value < 102)) return fail(c, PTMI_EINVAL, "pass groups must be 0 (automatic), 1 (every pass on its own), k in [2, 64] or 100 + g, g in [2, 64]");
-        c->opt_pass_groups = (int)value; return PTMI_OK;
-    case PTMI_OPT_CHAIN_SLOTS:
-        if (value != 0 && (value < 2 || value > 4096)) return fail(c, PTMI_EINVAL, "chain slots must be 0 (automatic) or in [2, 4096]");
-        c->opt_chain_slots = (int)value; return PTMI_OK;
-    case PTMI_OPT_PASS_HANDOFF:
-        if (value != PTMI_HANDOFF_FENCED && value != PTMI_HANDOFF_FENCE_FREE) return fail(c, PTMI_EINVAL, "unknown pass hand-off");
-        c->opt_pass_handoff = (int)value; return PTMI_OK;
-    case PTMI_OPT_BVH_DEVICE_BUILD:
-        if (value != PTMI_BVH_BUILD_EQUAL_COUNT && value != PTMI_BVH_BUILD_SPATIAL) return fail(c, PTMI_EINVAL, "unknown device build of the sphere hierarchy");
-        c->opt_bvh_build = (int)value; return PTMI_OK;
-    default: return fail(c, PTMI_EINVAL, "unknown option");
-    }
+    const Option *o = find_option(option);
+    if (!o) return fail(c, PTMI_EINVAL, "unknown option");
+    if (value < o->lo || value > o->hi || (o->but && o->but(value))) return fail(c, PTMI_EINVAL, o->refusal);
+    if (o->set) return o->set(c, (int)value);
+    c->*o->member = (int)value;
+    return PTMI_OK;
 }
 
 int ptmi_get_option(ptmi_ctx *c, int option, int64_t *value)
@@ -610,25 +601,10 @@ int ptmi_get_option(ptmi_ctx *c, int option, int64_t *value)
     if (!c) return PTMI_EINVAL;
     std::lock_guard<std::mutex> lock(c->mu);
     if (!value) return fail(c, PTMI_EINVAL, "value is NULL");
-    switch (option) {
-    case PTMI_OPT_STREAMS_SEED_RULE: *value = c->opt_seed_rule; return PTMI_OK;
-    case PTMI_OPT_STREAM_STEP_CAP:   *value = c->opt_step_cap; return PTMI_OK;
-    case PTMI_OPT_STREAM_CAPACITY:   *value = c->stream_form.rays_per_pixel(c->opt_capacity); return PTMI_OK;
-    case PTMI_OPT_STREAMS_FORM:      *value = c->opt_form; return PTMI_OK;
-    case PTMI_OPT_STREAM_BATCH:      *value = c->opt_batch; return PTMI_OK;
-    case PTMI_OPT_SPP_CHUNKS: *value = c->opt_spp_chunks; return PTMI_OK;
-    case PTMI_OPT_ARITHMETIC: *value = c->opt_arithmetic; return PTMI_OK;
-    case PTMI_OPT_STREAM_TAIL: *value = c->opt_tail_permille; return PTMI_OK;
-    case PTMI_OPT_ORDERED_PASSES: *value = c->opt_ordered_passes; return PTMI_OK;
-    case PTMI_OPT_GLASS_BATCH: *value = c->opt_glass_batch; return PTMI_OK;
-    case PTMI_OPT_STREAM_GRADED: *value = c->opt_graded; return PTMI_OK;
-    case PTMI_OPT_STREAM_PASS_GROUPS: *value = c->opt_pass_groups; return PTMI_OK;
-    case PTMI_OPT_SNAPSHOT_BUDGET_MB: *value = c->opt_snapshot_mb; return PTMI_OK;
-    case PTMI_OPT_CHAIN_SLOTS: *value = c->opt_chain_slots; return PTMI_OK;
-    case PTMI_OPT_PASS_HANDOFF: *value = c->opt_pass_handoff; return PTMI_OK;
-    case PTMI_OPT_BVH_DEVICE_BUILD: *value = c->opt_bvh_build; return PTMI_OK;
-    default: return fail(c, PTMI_EINVAL, "unknown option");
-    }
+    const Option *o = find_option(option);
+    if (!o) return fail(c, PTMI_EINVAL, "unknown option");
+    *value = o->get ? o->get(c) : c->*o->member;
+    return PTMI_OK;
 }
 
 static int seed_common(ptmi_ctx *c, uint64_t seed0, bool clear)
@@ -819,28 +795,7 @@ int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out)
     if (!out) return fail(c, PTMI_EINVAL, "out is NULL");
     PTMI_HIP(c, hipSetDevice(c->device));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned long long live = 0, sc[kScWords] = {0, 0, 0, 0}; unsigned int iters = 0;
-    std::vector<unsigned long long> live_shards((size_t)kStatShards * kStatStride);     // the sharded statistics: sum / maximum over the shards
-    std::vector<unsigned int> iter_shards((size_t)kStatShards * 2 * kStatStride);
-    PTMI_HIP(c, hipMemcpyAsync(live_shards.data(), c->d_live.p, kLiveBytes, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(sc, c->d_stream_counters.p, sizeof sc, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipMemcpyAsync(iter_shards.data(), c->d_iters.p, kItersBytes, hipMemcpyDeviceToHost, c->stream));
-    PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < kStatShards; ++k) {
-        live += live_shards[(size_t)k * kStatStride];
-        const unsigned int it = iter_shards[(size_t)k * 2 * kStatStride];
-        iters = it > iters ? it : iters;
-    }
-    const StreamFormState::Totals &form = c->stream_form.totals;
-    out->live_bounces = live + form.live_host; out->nominal_bounces = c->nominal; out->samples = c->samples;
-    out->stream_iterations = iters;
-    out->stream_rays_dropped = form.rays_dropped + sc[kScDropped];
-    out->stream_rays_truncated = form.rays_truncated + sc[kScTruncated];
-    out->stream_rays_spilled = form.rays_spilled;
-    out->stream_rays_overflowed = form.rays_overflowed;
-    out->last_render_ms = 0.0f;
-    if (c->timing && c->ev_valid) PTMI_HIP(c, hipEventElapsedTime(&out->last_render_ms, c->ev0, c->ev1));
-    return PTMI_OK;
+    return c->stats.read(c, out);
 }
 
 int ptmi_debug_counters_n(ptmi_ctx *c, uint32_t *out, int capacity)
@@ -851,7 +806,7 @@ int ptmi_debug_counters_n(ptmi_ctx *c, uint32_t *out, int capacity)
     if (capacity < 0) return fail(c, PTMI_EINVAL, "capacity is negative");
     const int words = capacity < kWorkWords ? capacity : kWorkWords;
     PTMI_HIP(c, hipSetDevice(c->device));
-    if (words > 0) PTMI_HIP(c, hipMemcpyAsync(out, c->d_work.p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (words > 0) PTMI_HIP(c, hipMemcpyAsync(out, c->stats.block[RenderStats::Work].p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     return words;
 }
@@ -868,11 +823,7 @@ int ptmi_reset_stats(ptmi_ctx *c)
     std::lock_guard<std::mutex> lock(c->mu);
     PTMI_HIP(c, hipSetDevice(c->device));
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_live.p, 0, kLiveBytes, c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_work.p, 0, kWorkWords * sizeof(unsigned int), c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_stream_counters.p, 0, kScWords * sizeof(unsigned long long), c->stream));
-    c->nominal = 0; c->samples = 0;
+    if (int rc = c->stats.reset(c)) return rc;
     c->stream_form.reset_totals();
     return PTMI_OK;
 }
@@ -933,11 +884,9 @@ int ptmi_eval_check_hit(ptmi_ctx *c, const float *rays, int n, float *t_out, int
     int32_t *d_idx = reinterpret_cast<int32_t *>(d_t + nb), *d_just = d_idx + nb;
     PTMI_HIP(c, hipStreamSynchronize(c->stream));
     PTMI_HIP(c, hipMemcpyAsync(d_rays, rays, nb * 6 * 4, hipMemcpyHostToDevice, c->stream));
-    SceneView scene;
-    scene.packed = c->scene.packed.as<float4>(); scene.n_spheres = (int)c->scene.rows.ns; scene.n_planes = (int)c->scene.rows.np;
-    scene.share_xy = c->scene.share_xy;
-    if (c->scene.kind == SceneKind::Mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(scene, c->scene.mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
-    else PTMI_HIP(c, launch_eval_check_hit(scene, c->scene.kind == SceneKind::Bvh ? &c->scene.bvh : nullptr, d_rays, n, d_t, d_idx, d_just, c->stream));
+    const RayCallScene r = ray_call_scene(c);
+    if (r.mesh) PTMI_HIP(c, launch_eval_check_hit_mesh(r.scene, *r.mesh, d_rays, n, d_t, d_idx, d_just, c->stream));
+    else PTMI_HIP(c, launch_eval_check_hit(r.scene, r.bvh, d_rays, n, d_t, d_idx, d_just, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(t_out, d_t, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(idx_out, d_idx, nb * 4, hipMemcpyDeviceToHost, c->stream));
     PTMI_HIP(c, hipMemcpyAsync(just_out, d_just, nb * 4, hipMemcpyDeviceToHost, c->stream));

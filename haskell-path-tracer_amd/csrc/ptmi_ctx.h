@@ -1,6 +1,7 @@
-// ptmi_ctx.h -- what the host units of the C ABI share: the context, its device blocks, the scene's device state, the chained closure's
-// states and what the stream form keeps between calls (internal; ptmi_api.cpp renders, ptmi_scene.cpp sets, moves and replaces geometry,
-// ptmi_chain.cpp holds states under tokens, ptmi_stream_call.cpp is the stream form of Streams).
+// ptmi_ctx.h -- what the host units of the C ABI share: the context, its device blocks, and the owners of its state -- the scene's device
+// state, the chained closure's states, what the stream form keeps between calls, the dispatch order and the statistics (internal;
+// ptmi_api.cpp renders, counts and holds the options, ptmi_scene.cpp sets, moves and replaces geometry, ptmi_chain.cpp holds states under
+// tokens, ptmi_stream_call.cpp is the stream form of Streams, ptmi_order.cpp the cost-ordered dispatch).
 #pragma once
 
 #include "../../include/ptmi.h"
@@ -160,6 +161,48 @@ struct StreamFormState {
     void destroy_handles();                          // the tail's events, then its stream (synchronised first)
 };
 
+struct RenderTarget;
+
+// The cost-ordered dispatch of the tiled kernels (ptmi_order.cpp; ptmi_device.h: lane_pixel): what every quad of tiles cost in the launches
+// made with one key -- (camera, scene, shape, limit, algorithm) -- and the order, most expensive first, later launches with that key use.
+// launch_render says which calls are ordered and brackets their launches with the first two functions; the stream form reads the next two.
+// Behind them: a rebuild of the order, or any change of its use, bumps the generation; another key, or blocks too small, start the count of
+// launches over; the count moves only once the launches went out; the tail's start word holds the number of quads -- no tail -- until the first rebuild.
+struct DispatchOrder {
+    // the blocks hold the target's quads, the costs are cleared or the order rebuilt, a.quad_order / a.quad_cost are set; a code as grow's
+    int before_launches(ptmi_ctx *c, const ptmi_camera &camera, uint64_t scene_version, const RenderTarget &target, int bounce_limit, int algorithm,
+                        bool stream_form, RenderArgs &a);
+    void launches_went_out() { launches = launches_after; }     // ... and after them: a call that failed in between repeats its step of the schedule
+    uint64_t generation() const { return generation_; }         // what a start-hit list made in this order is keyed by (StreamFormState::HitKey)
+    const unsigned int *tail_start() const { return tail_permille ? d_tail_start.as<unsigned int>() : nullptr; }   // the device word where the stream form's tail begins in the order; null: there is no tail
+    int &tail_option() { return tail_permille; }                // PTMI_OPT_STREAM_TAIL
+    template <class F> void each_block(F &&f) { for (DeviceBlock *b : {&d_quad_cost, &d_quad_order, &d_quad_class, &d_tail_start}) f(*b); }
+private:
+    DeviceBlock d_quad_cost, d_quad_order, d_quad_class, d_tail_start;   // unsigned int per quad; one word, written by the order kernel
+    struct Key { ptmi_camera cam; uint64_t scene_version; int dims[8]; } key{};
+    int launches = 0, launches_after = 0;                  // launches made with this key; ... once this call's went out
+    uint64_t generation_ = 0;
+    int tail_permille = -1;                                // thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
+};
+
+// The statistics of the render launches (ptmi_api.cpp): the kernels' counter blocks, what the host counts beside them, and the timing events.
+struct RenderStats {
+    enum { Live, Work, Iters, StreamCounters };            // RenderArgs.live_counter, work_counter, stream_iterations, stream_counters
+    DeviceBlock block[4];
+    static constexpr size_t kBytes[4] = {(size_t)kStatShards * kStatStride * sizeof(unsigned long long), kWorkWords * sizeof(unsigned int),       // (the first and the
+                                         (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int), kScWords * sizeof(unsigned long long)};   // third are sharded, ptmi_kernels.h)
+    uint64_t nominal = 0, samples = 0;
+    bool timing = false, ev_valid = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t create(hipStream_t stream, const char **failed_call);      // the events, the blocks, then stream-ordered zero fills
+    int reset(ptmi_ctx *c);
+    int read(ptmi_ctx *c, ptmi_stats *out);                               // the shard sums and maximum, the stream form's totals, the elapsed time
+    int launches_begin(ptmi_ctx *c, RenderArgs &a);                       // a call's launches: their counters, the two events around them ...
+    int launches_end(ptmi_ctx *c, uint64_t samples_made, uint64_t bounces_nominal);       // ... and what the call adds to the host's counts
+    template <class F> void each_block(F &&f) { for (DeviceBlock &b : block) f(b); }
+};
+constexpr size_t kItersBytes = RenderStats::kBytes[RenderStats::Iters];      // (the stream form clears RenderArgs.stream_iterations itself)
+
 }  // namespace ptmi
 
 struct ptmi_ctx {
@@ -182,27 +225,14 @@ struct ptmi_ctx {
     ptmi::SceneState scene;  // what is rendered (ptmi_scene.cpp)
     int opt_bvh_build = PTMI_BVH_BUILD_EQUAL_COUNT;   // PTMI_OPT_BVH_DEVICE_BUILD: which tree ptmi_set_bvh_spheres builds
 
-    DeviceBlock d_live;      // unsigned long long
-    DeviceBlock d_work;      // unsigned int
-    DeviceBlock d_iters;     // unsigned int
-    uint64_t nominal = 0, samples = 0;
-
-    bool timing = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_snap = nullptr;
-    DeviceBlock d_tail_start;   // unsigned int: where the stream form's tail begins in the dispatch order (written by the order kernel)
-    int opt_tail_permille = -1;                // PTMI_OPT_STREAM_TAIL: thousandths of the recorded cost the tail may hold (0 = no tail; -1 = automatic)
-    bool ev_valid = false;
+    ptmi::RenderStats stats;       // what the render launches count (ptmi_api.cpp)
+    hipEvent_t ev_snap = nullptr;  // ptmi_snapshot_color: orders a copy on another stream behind the renders
     int variant = ptmi::kVariantAuto;
     ptmi::Stager stager;                          // pinned ring + worker threads for host-buffer entry points (ptmi_stage.h)
 
-    // cost-ordered dispatch of the tiled kernels: what every quad of tiles cost in the last launch with this key, and
-    // the order (most expensive first) later launches with the same key use.  order_state = launches made with this key
-    DeviceBlock d_quad_cost, d_quad_order, d_quad_class;   // unsigned int per quad
-    int order_state = 0;
+    ptmi::DispatchOrder order;     // the cost-ordered dispatch of the tiled kernels (ptmi_order.cpp)
     DeviceBlock d_chunk_done;                  // sample chunks of the tiled Inline kernel: one word per tile workgroup, then the ticket counter's line
     unsigned int chunk_capacity() const { return d_chunk_done.bytes ? (unsigned int)(d_chunk_done.bytes / sizeof(unsigned int)) - 32u : 0u; }   // ... that many
-    struct OrderKey { ptmi_camera cam; uint64_t scene_version; int dims[8]; } order_key{};
-    uint64_t order_generation = 0;          // bumped whenever the dispatch order (d_quad_order, or its use) changes
 
     // scratch for ptmi_render1 / point queries
     DeviceBlock scratch;
@@ -211,9 +241,8 @@ struct ptmi_ctx {
     size_t device_memory = (size_t)64 << 30;   // bytes of the device (budget of the stream form's seed snapshots)
     DeviceBlock tree_stack;          // tree walk: the lanes' first waiting children (RenderArgs.tree_stack)
     ptmi::StreamFormState stream_form;   // the stream form's host side (ptmi_stream_call.cpp)
-    DeviceBlock d_stream_counters;   // kScWords device counters of the per-pixel Streams kernels
 
-    // options of render Streams (ptmi_set_option)
+    // options of render Streams (ptmi_set_option: one row of its table each; PTMI_OPT_STREAM_TAIL is the order's)
     int opt_seed_rule = PTMI_SEED_AUTO;              // resolved per scene: effective_seed_rule()
     int opt_step_cap = ptmi::kStreamStepCapDefault;
     int opt_capacity = 4;
@@ -234,9 +263,9 @@ struct ptmi_ctx {
     // Every DeviceBlock above: ptmi_destroy releases them all.  A new block is one more name here, or in its owner's each_block.
     template <class F> void each_block(F &&f)
     {
-        for (DeviceBlock *b : {&owned_block, &d_live, &d_work, &d_iters, &d_stream_counters, &d_tail_start, &d_quad_cost,
-                               &d_quad_order, &d_quad_class, &d_chunk_done, &scratch, &tree_stack})
-            f(*b);
+        for (DeviceBlock *b : {&owned_block, &d_chunk_done, &scratch, &tree_stack}) f(*b);
+        stats.each_block(f);
+        order.each_block(f);
         scene.each_block(f);
         stream_form.each_block(f);
         chain.each_block(f);
@@ -289,9 +318,9 @@ int effective_seed_rule(const ptmi_ctx *c);               // PTMI_OPT_STREAMS_SE
 // What the launcher of a caller-ray kernel takes of the context's scene (the ray queries, the paths, the stepped paths, the ray streams):
 // the packed rows, and the hierarchy of a BVH scene or of a mesh scene -- null otherwise
 struct RayCallScene { SceneView scene; const BvhView *bvh; const MeshView *mesh; };
+SceneView scene_view(const SceneState &s);
 RayCallScene ray_call_scene(const ptmi_ctx *c);
 int launch_render(ptmi_ctx *c, const RenderTarget &target, const ptmi_camera *camera, int algorithm, int bounce_limit, int n_spp);
-constexpr size_t kItersBytes = (size_t)kStatShards * 2 * kStatStride * sizeof(unsigned int);      // sharded statistics (ptmi_kernels.h)
 // `render Streams` in its stream form (ptmi_stream_call.cpp): launch_render's branch for it
 int render_streams_wavefront(ptmi_ctx *c, RenderArgs &a, int n_spp, const ptmi_camera &camera);
 

@@ -1,5 +1,6 @@
 // ptmi_stream_call.cpp -- the host side of `render Streams` in its stream ("wavefront") form: the pass schedules, one call's steps (StreamCall) and what the form
-// keeps between calls (StreamFormState, ptmi_ctx.h).  launch_render (ptmi_api.cpp) decides whether a call takes this form and in which dispatch order; the kernels are ptmi_stream_*.hip.
+// keeps between calls (StreamFormState, ptmi_ctx.h).  launch_render (ptmi_api.cpp) decides whether a call takes this form and whether in a dispatch order (DispatchOrder,
+// ptmi_order.cpp: its generation keys the start-hit list, its tail word is where the per-pixel tail begins); the kernels are ptmi_stream_*.hip.
 #include "ptmi_ctx.h"
 
 #include <algorithm>
@@ -184,7 +185,7 @@ int StreamCall::start_hit_list(const ptmi_camera &camera)
     // the statistics accumulate on the device over the whole call; cursors start from zero
     PTMI_HIP(c, hipMemsetAsync(qcount(), 0, (size_t)kLvWords * sizeof(unsigned int), c->stream));
     StreamFormState::HitKey key{};
-    key.cam = camera; key.scene_version = c->scene.version; key.order_generation = a.quad_order ? c->order_generation : 0;
+    key.cam = camera; key.scene_version = c->scene.version; key.order_generation = a.quad_order ? c->order.generation() : 0;
     const int key_dims[8] = {a.width, a.height, a.rows_local, a.stripe_rows, a.n_parts, a.part, a.quad_order ? 1 : 0, 0};
     std::memcpy(key.dims, key_dims, sizeof key_dims);
     key.region_slots = region_slots; key.cap_allows_split = a.stream_step_cap >= 3 ? 1 : 0; key.planes_r = nullptr;
@@ -232,8 +233,7 @@ int StreamCall::ordered_passes()
     // by the same arithmetic: no result depends on where the boundary lies.
     // (Only while a pixel's samples are ONE item: where they are cut into ordered passes the end of the launch is short already, and a
     // tail wave would render its tile's many samples in one piece -- 1080p / 256 spp: 16.99 ms with four passes, 17.86 with a tail beside them.)
-    const unsigned int *tail = (passes == 1 && c->opt_tail_permille != 0 && a.quad_order && c->d_tail_start.p && quad_positions(a.width, a.rows_local) > 0)
-                                   ? c->d_tail_start.as<unsigned int>() : nullptr;
+    const unsigned int *tail = (passes == 1 && a.quad_order && quad_positions(a.width, a.rows_local) > 0) ? c->order.tail_start() : nullptr;
     if (tail && !f.tail_stream) {
         int least = 0, greatest = 0;
         PTMI_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -243,7 +243,7 @@ int StreamCall::ordered_passes()
     }
     it.tail_start = tail;
     PTMI_HIP(c, launch_streams_advance_missed(a, hits, n_spp, tail, c->stream));
-    PTMI_HIP(c, hipMemsetAsync(c->d_iters.p, 0, kItersBytes, c->stream));
+    PTMI_HIP(c, hipMemsetAsync(a.stream_iterations, 0, kItersBytes, c->stream));
     if (tail) {
         PTMI_HIP(c, hipEventRecord(f.ev_fork, c->stream));
         PTMI_HIP(c, hipStreamWaitEvent(f.tail_stream, f.ev_fork, 0));
@@ -442,7 +442,7 @@ int StreamCall::fold_counters(unsigned long long overflowed)
     unsigned int longest = raw[(size_t)kLvDeepest * kCounterStride];            // stream_iterations: the deepest step of this call
     if (f.hit_split_pixels && longest < 2) longest = 2;                         // the children of the cached glass primary hits: traceStep 2
     if (longest == 0) longest = 1;                                              // every primary ray missed: one traceStep all the same
-    PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_iters.p), (int)longest, 1, c->stream));
+    PTMI_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.stream_iterations), (int)longest, 1, c->stream));
     return PTMI_OK;
 }
 
@@ -456,7 +456,7 @@ int split_passes(StreamCall &s)
         s.base[0] = s.it.out_base;
         PTMI_HIP(s.c, launch_streams_split(s.a, s.it, s.grid, s.c->stream));
         // stream_iterations lives in the per-pixel kernels' sharded counter: shard 0 carries this form's figure, copied on the device
-        if (attempt == 0) PTMI_HIP(s.c, hipMemsetAsync(s.c->d_iters.p, 0, kItersBytes, s.c->stream));
+        if (attempt == 0) PTMI_HIP(s.c, hipMemsetAsync(s.a.stream_iterations, 0, kItersBytes, s.c->stream));
         if (int rc = s.read_counters(1)) return rc;
         if (int rc = s.overflow_levels(overflowed)) return rc;
         const unsigned int dropped = s.raw[(size_t)kLvDropped * kCounterStride];

@@ -65,6 +65,8 @@ struct State {
     std::string log;                            // what was enqueued, in order, one line each (hipstub_log)
     struct Poke { std::string kernel; long nth; size_t offset; unsigned int value; bool armed; };
     std::vector<Poke> pokes;
+    struct KeptArg { std::string kernel; int index; std::vector<char> bytes; bool seen; };
+    std::vector<KeptArg> kept_args;             // hipstub_last_arg: the arguments asked for, as the latest launch gave them
     Stream null_stream{kStreamMagic, {}};
     std::set<Stream *> streams;                 // live streams (deferred mode: hipFree and hipMemcpy synchronise with all of them / the NULL one)
 };
@@ -213,6 +215,20 @@ const char *hipstub_log(void)
 }
 void hipstub_clear_log(void) { std::lock_guard<std::mutex> lock(g_mu); g_log.clear(); }
 void hipstub_clear_pokes(void) { std::lock_guard<std::mutex> lock(g_mu); S().pokes.clear(); }
+// The `bytes` bytes of argument `index` of the latest launch of a kernel whose name contains `kernel_part`, copied AT LAUNCH TIME (afterwards
+// they are gone: the launcher's stack).  The runtime does not know how long a kernel's arguments are, so the first query of a (kernel_part,
+// index) says how many bytes later launches keep; it, and every query before such a launch, returns 0 and leaves dst alone.  Otherwise 1.
+int hipstub_last_arg(const char *kernel_part, int index, void *dst, unsigned long long bytes)
+{
+    std::lock_guard<std::mutex> lock(g_mu);
+    for (State::KeptArg &k : S().kept_args) {
+        if (k.kernel != kernel_part || k.index != index || k.bytes.size() != bytes) continue;
+        if (k.seen) std::memcpy(dst, k.bytes.data(), bytes);
+        return k.seen ? 1 : 0;
+    }
+    S().kept_args.push_back(State::KeptArg{kernel_part, index, std::vector<char>((size_t)bytes), false});
+    return 0;
+}
 void hipstub_set_deferred(int on) { flush_all(); g_deferred = on != 0; }
 long hipstub_queued(void)                         // operations waiting for a synchronisation (deferred mode)
 {
@@ -267,6 +283,8 @@ hipError_t hipLaunchKernel(const void *function, dim3 grid, dim3 block, void **a
                     std::to_string(block.x) + "," + std::to_string(block.y) + "," + std::to_string(block.z) + " lds " + std::to_string(lds_bytes));
     for (State::Poke &p : S().pokes)
         if (!p.armed && name.find(p.kernel) != std::string::npos && --p.nth == 0) p.armed = true;
+    for (State::KeptArg &k : S().kept_args)
+        if (name.find(k.kernel) != std::string::npos) { std::memcpy(k.bytes.data(), args[k.index], k.bytes.size()); k.seen = true; }
     g_launch_seq = ++g_seq;
     return hipSuccess;
 }

@@ -22,18 +22,18 @@ import test_host_sanitized as hs  # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden", "chain_stream_calls.txt")
 
 
-def build_program(root=ROOT, pkg=None, out_dir=None):
-    """The program against the library of the checkout at `root` (the golden record is made from the parent commit's)."""
+def build_program(root=ROOT, pkg=None, out_dir=None, program="chain_stream_hostsan"):
+    """tests/cxx/<program>.cpp against the library of the checkout at `root` (the golden record is made from the parent commit's)."""
     pkg = pkg or graft.load_package()
     out_dir = out_dir or os.path.join(hs.OUT, "static")
     stub = hs.build_stub(out=os.path.join(out_dir, "libhipstub_plain.so"), sanitize=None)
     flags = [f for f in hs.HOST_SANITIZE if f != "-shared-libasan"]          # instrumented host code, no runtime of its own
     lib = pkg._build.build_lib(out=os.path.join(out_dir, "libptmi_sanitized_static.so"), extra_flags=flags)
-    out = os.path.join(out_dir, "chain_stream_hostsan")
+    out = os.path.join(out_dir, program)
     cmd = [hs.CLANG, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libsan",
            "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(root, "include"),
            "-I", os.path.join(root, "haskell-path-tracer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cxx", "chain_stream_hostsan.cpp"), "-o", out,
+           os.path.join(ROOT, "tests", "cxx", program + ".cpp"), "-o", out,
            stub, lib, "-Wl,-rpath," + out_dir]                # (the stand-in BEFORE the library: its hip* symbols win)
     res = subprocess.run(cmd, capture_output=True, text=True)
     assert res.returncode == 0, res.stdout + res.stderr

@@ -125,6 +125,30 @@ def test_cost_ordered_dispatch_changes_nothing_but_the_order(pkg, ora):
                 assert_planes_equal(c.download_state(), want, "after the scene change, launch %d" % k)
 
 
+def test_a_resize_in_mid_sequence_changes_nothing_but_the_order(pkg, ora):
+    """What the sequence above leaves out: one context is resized while its order stands.  64x16, the smallest tiled image, for three
+    launches (the costs cleared, the order built and rebuilt); 136x40 -- a partial tile column, a padded tile grid -- for three, for
+    which the order's blocks grow and its count starts over; back to 64x16, into blocks that are larger than it needs, under a key that
+    changed.  The planes equal the oracle's after every launch, for both algorithms."""
+    sp, pl = pkg.world.scene16()
+    cam = pkg.world.initial_camera()
+    limit = 8
+    for algorithm in (pkg.INLINE, pkg.STREAMS):
+        with pkg.Context(0) as c:
+            c.set_scene(sp, pl)
+            for w, h in ((64, 16), (136, 40), (64, 16)):
+                want = initial_planes(ora, w, h)
+                c.resize(w, h)
+                c.upload_state(*want)
+                for k in range(3):
+                    c.render(cam, limit, 1, algorithm)
+                    if algorithm == pkg.INLINE:
+                        want, _ = ora.render_inline(sp, pl, cam, w, h, limit, 1, want)
+                    else:
+                        want, _ = ora.render_streams(sp, pl, cam, w, h, 1 << 16, 1, want)
+                    assert_planes_equal(c.download_state(), want, "%dx%d, launch %d" % (w, h, k))
+
+
 @pytest.mark.parametrize("w,h,spp,chunks", [(96, 64, 7, 3), (333, 131, 12, 5), (200, 77, 64, 64), (64, 16, 5, 2), (1920, 1080, 9, 4)])
 def test_sample_chunks_change_no_bit(pkg, ora, w, h, spp, chunks):
     """PTMI_OPT_SPP_CHUNKS: the tile grid is launched `chunks` times over, copy c rendering a slice of the samples
