@@ -26,6 +26,7 @@ PTMI_OK, PTMI_EINVAL, PTMI_ENODEVICE, PTMI_EHIP, PTMI_ENOMEM, PTMI_ESTATE, PTMI_
 MAX_PRIMITIVES, MAX_BVH_SPHERES, MAX_BVH_PLANES, BVH_MAX_DEPTH, BVH_LEAF_MAX = 1024, 1 << 22, 64, 24, 4
 MAX_MESH_TRIANGLES = 1 << 22
 RAY_ORDER_MAX = 1 << 22
+MULTI_HIT_MAX = 16                                               # PTMI_MULTI_HIT_MAX: the longest list ptmi_trace_rays_multi_device keeps per ray
 RAY_KEY_NOT_PLACED = 1 << 44                                     # ptmi_ray_order_keys: a ray with a non-finite word or a zero direction
 # ptmi_bvh_node: the boxes of both children (centre, half extent), the child references, 1 / (2 r_min) per child
 BVH_NODE_DTYPE = np.dtype([("center", "<f4", (2, 3)), ("half", "<f4", (2, 3)), ("ref", "<i4", 2), ("inv_2r", "<f4", 2)])
@@ -144,6 +145,8 @@ SYMBOLS = {
     "ptmi_ray_order_keys": (C.c_int, [_vp, C.c_int, _vp]),
     "ptmi_trace_rays_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_occluded_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "ptmi_trace_rays_multi_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ptmi_trace_rays_multi_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "ptmi_path_seeds_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
     "ptmi_trace_paths_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ptmi_trace_paths_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
@@ -853,6 +856,41 @@ class Context:
         else:
             self._check(self._lib.ptmi_occluded_indexed_device(self._h, d_rays, d_t_max, n, d_index, int(index.shape[0]), d_out))
         return out
+
+    def trace_rays_multi(self, rays, k, t_max=None, out=None, index=None):
+        """ptmi_trace_rays_multi_device: the k nearest hits of every ray, in order, before its t_max (None: no limit), on the context's
+        stream.  rays as trace_rays takes them, 1 <= k <= MULTI_HIT_MAX, t_max a contiguous float32 device tensor of shape (n,).
+        -> (t, idx, count): t float32 (n, k) and idx int32 (n, k) -- row i the count[i] nearest hits ascending by (t, primitive), each
+        primitive once, then the miss record, t 0 and idx -1 -- and count int32 (n,).  They are allocated with torch.empty on the rays'
+        device unless out=(t, idx, count) gives the caller's own.
+        index: as for trace_rays (ptmi_trace_rays_multi_indexed_device); outputs allocated here are then filled with the miss record and
+        a count of 0 first."""
+        d_rays = _device_tensor(rays, "float32", (None, 6), "rays")
+        n = int(rays.shape[0])
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MULTI_HIT_MAX:
+            raise ValueError("k must be an int in [1, %d], not %r" % (MULTI_HIT_MAX, k))
+        d_t_max = _device_tensor(t_max, "float32", (n,), "t_max") if t_max is not None else None
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        if out is not None:
+            if len(out) != 3:
+                raise ValueError("out must be (t, idx, count)")
+            outs = tuple(out)
+        else:
+            import torch
+            if index is None:
+                outs = (torch.empty((n, k), dtype=torch.float32, device=rays.device), torch.empty((n, k), dtype=torch.int32, device=rays.device),
+                        torch.empty(n, dtype=torch.int32, device=rays.device))
+            else:
+                outs = (torch.zeros((n, k), dtype=torch.float32, device=rays.device), torch.full((n, k), -1, dtype=torch.int32, device=rays.device),
+                        torch.zeros(n, dtype=torch.int32, device=rays.device))
+        d_t = _device_tensor(outs[0], "float32", (n, k), "t")
+        d_idx = _device_tensor(outs[1], "int32", (n, k), "idx")
+        d_count = _device_tensor(outs[2], "int32", (n,), "count")
+        if index is None:
+            self._check(self._lib.ptmi_trace_rays_multi_device(self._h, d_rays, d_t_max, n, k, d_t, d_idx, d_count))
+        else:
+            self._check(self._lib.ptmi_trace_rays_multi_indexed_device(self._h, d_rays, d_t_max, n, d_index, int(index.shape[0]), k, d_t, d_idx, d_count))
+        return outs
 
     def ray_order(self, rays, out=None, work=None):
         """ptmi_ray_order_device: a coherent order for the batch, on the context's stream, nothing leaving the device -> an int32 device

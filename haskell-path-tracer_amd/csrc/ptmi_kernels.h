@@ -275,6 +275,12 @@ hipError_t launch_trace_rays_indexed(SceneView scene, const BvhView *bvh, const 
                                      float *t, int32_t *idx, float *hit, hipStream_t stream);
 hipError_t launch_occluded_indexed(SceneView scene, const BvhView *bvh, const MeshView *mesh, float reach, const float *rays, const float *t_max, int n,
                                    const int32_t *index, int m, int32_t *occluded, hipStream_t stream);
+// The k nearest hits along a caller's rays (ptmi_trace_rays_multi_device, ptmi_trace_rays_multi_indexed_device; ptmi_multi_hit.hip): one lane per
+// ray -- per entry of `index` when that is not null, an entry outside [0, n) skipped -- writes row i of t and idx (n x k words) and count[i].
+// t_max: n words, or null for +inf.  Rows are stored in 16-byte pieces when k % 4 == 0 and t and idx are 16-byte aligned.  Nothing is
+// launched for n or m <= 0 or a k outside [1, PTMI_MULTI_HIT_MAX].
+hipError_t launch_trace_rays_multi(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, const float *t_max, int n,
+                                   const int32_t *index, int m, int k, float *t, int32_t *idx, int32_t *count, hipStream_t stream);
 // Render Inline along a caller's rays (ptmi_trace_paths_device, ptmi_trace_paths_indexed_device; ptmi_paths.hip): one lane per ray -- per entry
 // of `index` when that is not null, an entry outside [0, n) skipped -- adds n_spp samples of traceInline to color[i] (n x 3 words) and
 // advances seed[i] (n x 4 words: a, b, c, counter).  Nothing is launched for n, m or n_spp <= 0.  path_seeds: seed[i] = genSeeds' state of

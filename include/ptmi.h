@@ -792,6 +792,36 @@ int ptmi_trace_rays_indexed_device(ptmi_ctx *ctx, const float *d_rays, int n, co
 int ptmi_occluded_indexed_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m,
                                  int32_t *d_occluded);
 
+/* ---- multi-hit: the k nearest hits along a caller's rays ----------------------- */
+/* The first k hits in order, within t_max: what lies between a point and a light (a shadow ray through GLASS), every return along a
+ * sensor's beam, the ordered crossings of a thickness query.  The order, lifetime and refusal rules are ptmi_trace_rays_device's: one
+ * launch on the context's stream, no host wait, no allocation, no copy.  d_t and d_idx hold n x k words (row i at k i), d_count n.
+ *   - QUALIFYING HITS.  For ray i with lim = d_t_max ? d_t_max[i] : +inf, H is the set of pairs (t_j, j) over ALL primitives j of the
+ *     scene -- spheres, then planes, then triangles -- whose own test is a Just and whose t_j < lim, one binary32 compare.  The own tests
+ *     are the closest hit's, from the same text: a sphere's distanceTo with the correctly rounded root and !(t < 0), a plane's behind the
+ *     candidate test !(denom > 1e-6), the triangle test, a zero-area triangle never a Just.  Each primitive contributes at most one hit:
+ *     a sphere gives its entry point only.  A NaN t fails the compare, and +inf fails it against any lim: every listed t is finite and
+ *     >= 0, and a NaN or non-positive t_max gives an empty list.
+ *   - THE OUTPUT.  d_count[i] = min(k, |H|); row i of d_t and d_idx holds the d_count[i] smallest elements of H ascending by (t, j),
+ *     lexicographically -- at equal t the lower primitive index first, the closest hit's tie rule -- and the rest of the row the miss
+ *     record, t = 0 and idx = -1.
+ *   - Where no primitive's key for the ray is a NaN, column 0 at k = 1 without d_t_max is ptmi_trace_rays_device's (t, idx), and
+ *     d_count > 0 at k = 1 is ptmi_occluded_device under the same t_max.
+ *   - ptmi_trace_rays_multi_indexed_device: lane p < m takes i = d_index[p]; an entry outside [0, n) is skipped, the answer goes to row
+ *     i with the plain entry's words, and a position no entry names is left untouched.
+ *   - Refusals enqueue and write nothing: PTMI_ESTATE before a scene is set; PTMI_EINVAL for a negative n or m, for k < 1 and for a NULL
+ *     required pointer with work to do (d_t_max may be NULL); PTMI_ELIMIT for k > PTMI_MULTI_HIT_MAX.  n == 0 or m == 0 is PTMI_OK and
+ *     touches nothing.  The context's planes, statistics and dispatch order are left alone.
+ *   - A hierarchy's walk is bounded by the k-th key the lane holds, so k = 1 costs about a closest hit and a larger k walks further;
+ *     without t_max and with k above the hits there are, the walk visits everything the ray's boxes touch (csrc/ptmi_multi_hit_device.h
+ *     has the argument, DESIGN.md 5.9 the measurements).
+ *   - There is no group form, as above. */
+#define PTMI_MULTI_HIT_MAX 16
+int ptmi_trace_rays_multi_device(ptmi_ctx *ctx, const float *d_rays /* [n][6] */, const float *d_t_max /* [n], or NULL: +inf for every ray */,
+                                 int n, int k, float *d_t /* [n][k] */, int32_t *d_idx /* [n][k] */, int32_t *d_count /* [n] */);
+int ptmi_trace_rays_multi_indexed_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m,
+                                         int k, float *d_t, int32_t *d_idx, int32_t *d_count);
+
 /* ---- paths along a caller's rays ---------------------------------------------- */
 /* The third question about a caller's own device-resident rays, the one only a camera could ask so far: what light arrives along this ray
  * (traceInline, src/Scene/Trace.hs:344-383).  It serves cameras ptmi_camera cannot describe (fisheye, orthographic, thin lens), jittered
