@@ -24,17 +24,17 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libptmi.so")
 ABLATIONS_LIB = os.path.join(HERE, "libptmi_ablations.so")   # the same library with the ablation kernels of DESIGN.md 5.2 (tests, measurements)
 OBJ_ROOT = os.path.join(ROOT, "build", "obj")
-HOST_SOURCES = ["ptmi_api.cpp", "ptmi_order.cpp", "ptmi_chain.cpp", "ptmi_stream_call.cpp", "ptmi_scene.cpp", "ptmi_stage.cpp", "ptmi_group.cpp", "ptmi_bvh.cpp", "ptmi_mesh.cpp", "ptmi_ray_order.cpp", "ptmi_bounce.cpp", "ptmi_trace_streams.cpp", "ptmi_multi_hit.cpp"]
+HOST_SOURCES = ["ptmi_api.cpp", "ptmi_order.cpp", "ptmi_chain.cpp", "ptmi_stream_call.cpp", "ptmi_scene.cpp", "ptmi_stage.cpp", "ptmi_group.cpp", "ptmi_bvh.cpp", "ptmi_mesh.cpp", "ptmi_ray_order.cpp", "ptmi_bounce.cpp", "ptmi_trace_streams.cpp", "ptmi_multi_hit.cpp", "ptmi_nearest.cpp"]
 BUILD_ID_UNIT = "ptmi_build_id.cpp"                          # ptmi_build_id(): compiled at every link with -DPTMI_BUILD_ID=<the code the library holds>
 BUILD_ID_MARKER = b"PTMI_BUILD_ID="                          # ... behind this marker in the binary, so that the file can be asked without loading it
 SOURCE_HASH_MARKER = b"PTMI_SOURCE_HASH="                    # ... and the hash of the source TEXT it was linked from (staleness only, see source_hash)
 INLINE_UNIT = "ptmi_inline.hip"                              # also the contracted-arithmetic object
 KERNEL_UNITS = [INLINE_UNIT, "ptmi_streams_chain.hip", "ptmi_streams_tree.hip", "ptmi_stream_primary.hip", "ptmi_stream_pixels.hip",
                 "ptmi_stream_split.hip", "ptmi_small.hip", "ptmi_mesh_refit.hip", "ptmi_mesh_build.hip", "ptmi_bvh_refit.hip", "ptmi_bvh_build.hip", "ptmi_bvh_lbvh.hip", "ptmi_query.hip",
-                "ptmi_query_indexed.hip", "ptmi_ray_order.hip", "ptmi_paths.hip", "ptmi_bounce.hip", "ptmi_trace_streams.hip", "ptmi_multi_hit.hip"]
+                "ptmi_query_indexed.hip", "ptmi_ray_order.hip", "ptmi_paths.hip", "ptmi_bounce.hip", "ptmi_trace_streams.hip", "ptmi_multi_hit.hip", "ptmi_nearest.hip"]
 ABLATION_UNITS = ["ptmi_inline_ablations.hip"]               # only with -DPTMI_ABLATIONS
 SOURCES = HOST_SOURCES + [BUILD_ID_UNIT] + KERNEL_UNITS + ABLATION_UNITS
-HEADERS = ["ptmi_core.h", "ptmi_ctx.h", "ptmi_kernels.h", "ptmi_device.h", "ptmi_bvh_device.h", "ptmi_bvh.h", "ptmi_bvh_box.h", "ptmi_bvh_spatial.h", "ptmi_mesh_device.h", "ptmi_query_device.h", "ptmi_ray_lane_device.h", "ptmi_multi_hit_device.h", "ptmi_mesh.h", "ptmi_mesh_box.h", "ptmi_mesh_morton.h", "ptmi_ray_order.h", "ptmi_inline_body.inc", "ptmi_streams_chain_body.inc", "ptmi_streams_tree_body.inc", "ptmi_diag.h", "ptmi_stream_form.h", "ptmi_stage.h", "ptmi_share.h",
+HEADERS = ["ptmi_core.h", "ptmi_ctx.h", "ptmi_kernels.h", "ptmi_device.h", "ptmi_bvh_device.h", "ptmi_bvh.h", "ptmi_bvh_box.h", "ptmi_bvh_spatial.h", "ptmi_mesh_device.h", "ptmi_query_device.h", "ptmi_ray_lane_device.h", "ptmi_multi_hit_device.h", "ptmi_nearest.h", "ptmi_nearest_device.h", "ptmi_mesh.h", "ptmi_mesh_box.h", "ptmi_mesh_morton.h", "ptmi_ray_order.h", "ptmi_inline_body.inc", "ptmi_streams_chain_body.inc", "ptmi_streams_tree_body.inc", "ptmi_diag.h", "ptmi_stream_form.h", "ptmi_stage.h", "ptmi_share.h",
            os.path.join("..", "..", "include", "ptmi.h")]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                  "-fno-fast-math", "-fno-slp-vectorize", "-DPTMI_SINCOS_FUSED=1", "-Wall", "-pthread"]

@@ -147,6 +147,9 @@ SYMBOLS = {
     "ptmi_occluded_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
     "ptmi_trace_rays_multi_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "ptmi_trace_rays_multi_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ptmi_nearest_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_nearest_indexed_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "ptmi_nearest": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ptmi_path_seeds_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
     "ptmi_trace_paths_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ptmi_trace_paths_indexed_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
@@ -340,6 +343,34 @@ def live_rays(throughput, index=None, out=None):
     if rc != PTMI_OK:
         raise PtmiError(rc, "ptmi_live_rays")
     return out, int(count.value)
+
+
+def nearest(spheres, planes, triangles, points, r_max=None, point=False):
+    """ptmi_nearest: the nearest-primitive query's host twin (host code, no device) -- for every point the primitive with the least
+    (|signed distance|, index) within its r_max, by enumeration.  spheres, planes, triangles: arrays of the scene dtypes (any may be empty
+    or None, not all); points: float32 (n, 3); r_max: float32 (n,) or None for no limit.
+    -> (dist, idx), or (dist, idx, point) with point=True: dist float32 (n,) the signed distance, negative behind the surface; idx int32
+    (n,) -- spheres, then planes, then triangles; a miss is dist 0, idx -1, location (0, 0, 0) -- and point float32 (n, 3), the nearest
+    location on the primitive."""
+    s = np.ascontiguousarray(spheres if spheres is not None else [], dtype=SPHERE_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(planes if planes is not None else [], dtype=PLANE_DTYPE).reshape(-1)
+    t = np.ascontiguousarray(triangles if triangles is not None else [], dtype=TRIANGLE_DTYPE).reshape(-1)
+    pts = np.asarray(points)
+    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] != 3 or not pts.flags.c_contiguous:
+        raise ValueError("points must be a contiguous float32 array of shape (n, 3), not %s %r" % (pts.dtype, pts.shape))
+    n = pts.shape[0]
+    if r_max is not None:
+        r_max = np.asarray(r_max)
+        if r_max.dtype != np.float32 or r_max.shape != (n,) or not r_max.flags.c_contiguous:
+            raise ValueError("r_max must be a contiguous float32 array of shape (%d,), not %s %r" % (n, r_max.dtype, r_max.shape))
+    dist, idx = np.zeros(n, np.float32), np.zeros(n, np.int32)
+    at = np.zeros((n, 3), np.float32) if point else None
+    rc = load_library().ptmi_nearest(_ptr(s) if s.size else None, s.size, _ptr(pl) if pl.size else None, pl.size, _ptr(t) if t.size else None, t.size,
+                                     _ptr(pts) if n else None, _ptr(r_max) if r_max is not None and n else None, n, _ptr(dist) if n else None,
+                                     _ptr(idx) if n else None, _ptr(at) if point and n else None)
+    if rc != PTMI_OK:
+        raise PtmiError(rc, "ptmi_nearest")
+    return (dist, idx, at) if point else (dist, idx)
 
 
 def _device_rows(t, words, what):
@@ -890,6 +921,43 @@ class Context:
             self._check(self._lib.ptmi_trace_rays_multi_device(self._h, d_rays, d_t_max, n, k, d_t, d_idx, d_count))
         else:
             self._check(self._lib.ptmi_trace_rays_multi_indexed_device(self._h, d_rays, d_t_max, n, d_index, int(index.shape[0]), k, d_t, d_idx, d_count))
+        return outs
+
+    def nearest(self, points, r_max=None, point=False, out=None, index=None):
+        """ptmi_nearest_device: the nearest-primitive query -- for every point the primitive of the current scene with the least
+        (|signed distance|, index) within its r_max (None: no limit), on the context's stream, nothing leaving the device.  points: a
+        contiguous float32 device tensor of shape (n, 3), r_max one of shape (n,); ordering and lifetime as for trace_rays.
+        -> (dist, idx), or (dist, idx, point) with point=True: dist float32 (n,), the signed distance, negative behind the surface; idx
+        int32 (n,) -- spheres, then planes, then triangles; a miss is dist 0, idx -1, location (0, 0, 0) -- and point float32 (n, 3), the
+        nearest location on the primitive.  They are allocated with torch.empty on the points' device unless out=(dist, idx) or
+        out=(dist, idx, point) gives the caller's own.
+        index: as for trace_rays (ptmi_nearest_indexed_device); outputs allocated here are then filled with the miss record first."""
+        d_points = _device_tensor(points, "float32", (None, 3), "points")
+        n = int(points.shape[0])
+        d_r_max = _device_tensor(r_max, "float32", (n,), "r_max") if r_max is not None else None
+        d_index = _device_tensor(index, "int32", (None,), "index") if index is not None else None
+        if out is not None:
+            if len(out) not in (2, 3):
+                raise ValueError("out must be (dist, idx) or (dist, idx, point)")
+            point = len(out) == 3
+            outs = tuple(out)
+        else:
+            import torch
+            if index is None:
+                outs = (torch.empty(n, dtype=torch.float32, device=points.device), torch.empty(n, dtype=torch.int32, device=points.device))
+                if point:
+                    outs += (torch.empty((n, 3), dtype=torch.float32, device=points.device),)
+            else:
+                outs = (torch.zeros(n, dtype=torch.float32, device=points.device), torch.full((n,), -1, dtype=torch.int32, device=points.device))
+                if point:
+                    outs += (torch.zeros((n, 3), dtype=torch.float32, device=points.device),)
+        d_dist = _device_tensor(outs[0], "float32", (n,), "dist")
+        d_idx = _device_tensor(outs[1], "int32", (n,), "idx")
+        d_at = _device_tensor(outs[2], "float32", (n, 3), "point") if point else None
+        if index is None:
+            self._check(self._lib.ptmi_nearest_device(self._h, d_points, d_r_max, n, d_dist, d_idx, d_at))
+        else:
+            self._check(self._lib.ptmi_nearest_indexed_device(self._h, d_points, d_r_max, n, d_index, int(index.shape[0]), d_dist, d_idx, d_at))
         return outs
 
     def ray_order(self, rays, out=None, work=None):

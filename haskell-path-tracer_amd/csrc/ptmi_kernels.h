@@ -281,6 +281,11 @@ hipError_t launch_occluded_indexed(SceneView scene, const BvhView *bvh, const Me
 // launched for n or m <= 0 or a k outside [1, PTMI_MULTI_HIT_MAX].
 hipError_t launch_trace_rays_multi(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *rays, const float *t_max, int n,
                                    const int32_t *index, int m, int k, float *t, int32_t *idx, int32_t *count, hipStream_t stream);
+// The nearest-primitive query over a caller's points (ptmi_nearest_device, ptmi_nearest_indexed_device; ptmi_nearest.hip): one lane per point --
+// per entry of `index` when that is not null, an entry outside [0, n) skipped -- writes dist[i], idx[i] and, unless `point` is null, the
+// nearest location into point[3 i ..].  r_max: n words, or null for +inf.  Nothing is launched for n or m <= 0.
+hipError_t launch_nearest(SceneView scene, const BvhView *bvh, const MeshView *mesh, const float *points, const float *r_max, int n, const int32_t *index, int m,
+                          float *dist, int32_t *idx, float *point, hipStream_t stream);
 // Render Inline along a caller's rays (ptmi_trace_paths_device, ptmi_trace_paths_indexed_device; ptmi_paths.hip): one lane per ray -- per entry
 // of `index` when that is not null, an entry outside [0, n) skipped -- adds n_spp samples of traceInline to color[i] (n x 3 words) and
 // advances seed[i] (n x 4 words: a, b, c, counter).  Nothing is launched for n, m or n_spp <= 0.  path_seeds: seed[i] = genSeeds' state of

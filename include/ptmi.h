@@ -54,7 +54,8 @@ extern "C" {
                             * PTMI_BVH_BUILD_*, ptmi_bvh_layout_spatial); the ray queries on device-resident rays (ptmi_trace_rays_device,
                             * ptmi_occluded_device); paths along device-resident rays (ptmi_trace_paths_device,
                             * ptmi_trace_paths_indexed_device, ptmi_path_seeds_device); those paths one bounce at a time and the list
-                            * of live rays (ptmi_bounce_rays_device, ptmi_bounce_rays_indexed_device, ptmi_live_rays_device). */
+                            * of live rays (ptmi_bounce_rays_device, ptmi_bounce_rays_indexed_device, ptmi_live_rays_device); the
+                            * nearest-primitive query (ptmi_nearest_device, ptmi_nearest_indexed_device, ptmi_nearest). */
 
 /* ---- error codes ------------------------------------------------------------ */
 enum {
@@ -821,6 +822,47 @@ int ptmi_trace_rays_multi_device(ptmi_ctx *ctx, const float *d_rays /* [n][6] */
                                  int n, int k, float *d_t /* [n][k] */, int32_t *d_idx /* [n][k] */, int32_t *d_count /* [n] */);
 int ptmi_trace_rays_multi_indexed_device(ptmi_ctx *ctx, const float *d_rays, const float *d_t_max, int n, const int32_t *d_index, int m,
                                          int k, float *d_t, int32_t *d_idx, int32_t *d_count);
+
+/* ---- the nearest-primitive query: the primitive nearest to a caller's points ---- */
+/* The companion of the ray queries: which primitive is nearest to this point, how far away is it, and where on it is the nearest location --
+ * the clearance of a sensor from the scene, a distance field sampled into a grid, points snapped to surfaces, "is anything within r of
+ * here".  d_points holds n x 3 words, d_r_max n (or NULL), d_dist and d_idx n, d_point n x 3 (or NULL: no locations wanted).  The order,
+ * lifetime and refusal rules are ptmi_trace_rays_multi_device's: one launch on the context's stream, no host wait, no allocation, no
+ * copy; 4-byte alignment suffices for every array.
+ *   - THE ANSWER.  For point i with lim = d_r_max ? d_r_max[i] : +inf, every primitive j of the current scene -- linear, BVH or mesh;
+ *     spheres, then planes, then triangles -- has a signed distance s_j and the key |s_j|, and the answer is the minimum of (key, j),
+ *     lexicographically (at equal keys the lower index), over the primitives with key < lim, one binary32 compare.  A NaN or +inf key
+ *     never qualifies; a NaN or non-positive r_max gives a miss.  d_dist[i] = s_j, NEGATIVE BEHIND THE SURFACE (inside a sphere, behind a
+ *     plane's or a triangle's front), d_idx[i] = j and d_point[i] the nearest location on primitive j.  A miss is dist 0, idx -1,
+ *     location (0, 0, 0).
+ *   - THE DISTANCES are binary32, every operation rounded on its own, on coordinates RELATIVE TO THE POINT, so that their error is a
+ *     small multiple of 2^-24 times the distance to the primitive's farthest point, wherever the scene lies (csrc/ptmi_nearest.h, the
+ *     one definition of device and host).  A sphere (c, r): |p - c| - r, the location c + (p - c) r / |p - c|, at the centre
+ *     (cx + r, cy, cz).  A plane: dot(p - pos, dir) / |dir|, dir as stored and divided by its length here; a zero or non-finite
+ *     direction is no candidate.  A triangle: the distance to its plane where p's foot on the plane lies inside or on an edge, otherwise
+ *     the least distance to its three edges; its normal is formed from the relative coordinates with compensated products, so a needle
+ *     or a sliver is served as accurately as any other shape; negative when p is behind the front.  A triangle of zero area is no
+ *     candidate, as for rays.
+ *   - ptmi_nearest_indexed_device: lane k < m takes i = d_index[k]; an entry outside [0, n) is skipped, the answer goes to position i,
+ *     and a position no entry names is left untouched.
+ *   - Refusals enqueue and write nothing: PTMI_ESTATE before a scene is set; PTMI_EINVAL for a negative n or m and for a NULL required
+ *     pointer with work to do (d_r_max and d_point may be NULL).  n == 0 or m == 0 is PTMI_OK and touches nothing.  The context's
+ *     planes, statistics and dispatch order are left alone.
+ *   - A hierarchy's walk is bounded by the best key so far, which starts at r_max: a small r_max visits little, and a point far from
+ *     everything without one visits much (csrc/ptmi_nearest_device.h has the argument that the winner is never pruned).  A point with a
+ *     non-finite word, or farther than 2^40 from a hierarchy's box, enumerates every primitive.
+ *   - ptmi_nearest is the HOST TWIN: no context, no device; the same answers by enumeration, from the same functions -- the definition
+ *     the device entries are held to.  r_max and point may be NULL.  With triangles it refuses what ptmi_set_scene_mesh refuses in the
+ *     scene data, by that call's own checks: counts beyond PTMI_MAX_BVH_* and PTMI_MAX_MESH_TRIANGLES (PTMI_ELIMIT), an unknown brdf_tag,
+ *     non-finite sphere or triangle geometry, a non-finite triangle material (PTMI_EINVAL); without triangles it takes the data as a
+ *     linear scene does.  An empty scene, a negative count or a NULL required pointer with work to do is PTMI_EINVAL.
+ *   - There is no group form, as above. */
+int ptmi_nearest_device(ptmi_ctx *ctx, const float *d_points /* [n][3] */, const float *d_r_max /* [n], or NULL: +inf for every point */, int n,
+                        float *d_dist /* [n] */, int32_t *d_idx /* [n] */, float *d_point /* [n][3], may be NULL */);
+int ptmi_nearest_indexed_device(ptmi_ctx *ctx, const float *d_points, const float *d_r_max, int n, const int32_t *d_index, int m,
+                                float *d_dist, int32_t *d_idx, float *d_point);
+int ptmi_nearest(const ptmi_sphere *spheres, int n_spheres, const ptmi_plane *planes, int n_planes, const ptmi_triangle *triangles, int n_triangles,
+                 const float *points, const float *r_max, int n, float *dist, int32_t *idx, float *point);
 
 /* ---- paths along a caller's rays ---------------------------------------------- */
 /* The third question about a caller's own device-resident rays, the one only a camera could ask so far: what light arrives along this ray
